@@ -15,12 +15,16 @@ path: sample -> rollout+cost -> weights+reduce -> finalize, with every input res
 
 Prints ONE JSON line on rank 0.  `value` = sample-steps/s (N_total * T * solves/s), whole job.
 `roofline` is for the dominant kernel (rollout_cost_kernel), measured with HIP events on the launch
-stream inside the timed region.  At N=1, rank 0 also reports, in the same line:
+stream inside the timed region.  A plain run does only what `value` needs: set-up, warm-up, the K timed steps, the line.
+`--dump-outputs DIR` also writes what the last timed step returned (action_seq.npy, state_seq.npy; float32).
+`--full` adds everything else: the per-stage pass (`stages_ms`, `solve_roofline`), `long_run` (--steps < 200) and, at N > 1,
+the strong-scaling leg; at N=1 rank 0 also reports, in the same line:
   cpu_baseline        the oracle (C restatement of the reference algorithm, OpenMP over samples) on this host
   cpu_baseline_torch  the reference's own op structure (per-timestep Python loops of batched torch ops) over the same
                       plugins on this host: best of a thread-count scan + the all-cores figure (SURVEY 8d / BASELINE.md 3)
   closed_loop         >= 100 racing control ticks: reference window recomputed, solve, a[0] applied (example/racing.py:221-266)
   other_configs       solve times of BASELINE configs C1 / C2 / C5
+(--no-cpu-baseline / --no-extras drop the first two / the others from a --full run.)
 """
 import argparse
 import json
@@ -37,6 +41,23 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6290 GB/s measured copy
 SETUP_SOLVES = int(os.environ.get("MPPI_BENCH_SETUP_SOLVES", "200"))  # un-timed solves before the contract's warm-up: leave the idle power state (see main)
+EVENT_POOL_PAIRS = 8192  # HIP-event pairs the library keeps per timed stage (csrc StageTimer: 16 384 events); later stages go untimed
+
+
+def dump_dir(args):
+    """Where --dump-outputs writes: DIR itself, or DIR/<transport> in a transport's own process (N > 1, --exchange all), whose
+    parent copies the best transport's files up into DIR (orchestrate_transports)."""
+    child = os.environ.get("MPPI_BENCH_CHILD")
+    return os.path.join(args.dump_outputs, child) if child else args.dump_outputs
+
+
+def write_outputs(path, arrays):
+    """DIR/<name>.npy for every array the timed path returned from its last step."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 _LINE_FD = None
@@ -295,6 +316,12 @@ def orchestrate_transports(args, world, rank, order, run_child=run_child_transpo
         print_line(json.dumps(null_line(args, world, "no transport completed a run (each ran in its own process)", entries)))
         return 1
     best = max(lines, key=lambda m: lines[m]["value"])
+    if getattr(args, "dump_outputs", None):
+        import shutil
+
+        src = os.path.join(args.dump_outputs, best)
+        for f in os.listdir(src):
+            shutil.copy(os.path.join(src, f), os.path.join(args.dump_outputs, f))
     out = dict(lines[best])
     out["transports"] = entries
     out.setdefault("config", {})["exchange_requested"] = "all (one process per transport)"
@@ -365,8 +392,17 @@ def main():
                          "the metric's workload with a dense softmax (lambda = 5000) (profiling aids: print a short line, not "
                          "the contract's)")
     ap.add_argument("--timing", type=int, default=2, help="HIP-event instrumentation inside the timed region: "
-                    "1 = every stage, 2 = dominant kernel only, 0 = none (stage times from a second pass)")
+                    "1 = every stage, 2 = dominant kernel only, 0 = none (--full: stage times from a second pass)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: the per-stage pass, long_run, the extras (closed_loop, "
+                         "other_configs, ...), the CPU baselines and, at N > 1, the strong-scaling leg (off: set-up, "
+                         "warm-up, the K timed steps and the line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (the metric's workload) as "
+                         "DIR/action_seq.npy and DIR/state_seq.npy (float32)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "c3":
+        ap.error("--dump-outputs writes the outputs of the metric's workload (--workload c3)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -488,7 +524,7 @@ def main():
         # (the HIP events of --timing are created on demand, ~3 us each: the set-up solves run instrumented so that the pool exists
         # before the timed region — 40 creations inside a 20-step region were 6 us per step of round 5's headline)
         solver.set_option("timing", args.timing)
-        for _ in range(max(SETUP_SOLVES, args.steps)):
+        for _ in range(max(SETUP_SOLVES, min(args.steps, EVENT_POOL_PAIRS))):
             solver.forward(x0)
         sync()
         solver.stage_times_ms()  # drain (the events stay in the pool)
@@ -502,9 +538,12 @@ def main():
         solver.join_state_seq()  # (lazy state sequences: all K of them are completed INSIDE the timed region)
         sync()
         dt = time.perf_counter() - t0
+        # (copied now: later solves on this solver overwrite the tensors forward() returned)
+        outputs = {"action_seq": a.detach().cpu().numpy(), "state_seq": s.detach().cpu().numpy()} if args.dump_outputs else None
         stages = solver.stage_times_ms()
         t_exchange_ms = None
-        if args.timing != 1:  # complete the per-stage picture with a separate instrumented pass
+        all_stages = args.timing == 1 or args.full
+        if args.timing != 1 and args.full:  # complete the per-stage picture with a separate instrumented pass
             solver.set_option("timing", 1)
             n2 = min(args.steps, 50)
             t1 = time.perf_counter()
@@ -545,12 +584,14 @@ def main():
             else:
                 rccl_ranks = {"world_size": dist.get_world_size(), "backend": dist.get_backend(),
                               "communicator": "torch.distributed process group"}
-        return {"exchange": used, "requested": mode, "dt": dt, "stages": stages, "exchange_ms": t_exchange_ms, "finite": finite,
+        return {"exchange": used, "requested": mode, "dt": dt, "stages": stages, "all_stages": all_stages,
+                "exchange_ms": t_exchange_ms, "finite": finite, "outputs": outputs,
                 "ctrl": ctrl, "n_total": n_total, "rank_stages": rank_stages, "rccl_ranks": rccl_ranks,
                 "solver_kwargs": {k: v for k, v in dkw.items() if not k.startswith("_")}}
 
     def compose(best, runs):
-        """The contract's JSON line from the best complete run (rank 0)."""
+        """The contract's JSON line from the best complete run (rank 0).  `roofline` / `valu_roofline` need the dominant
+        kernel's event time, `stages_ms` / `solve_roofline` every stage's (see timed_run)."""
         dt, stages, solver = best["dt"], best["stages"], best["ctrl"].solver
         ms_per_step = dt / args.steps * 1e3
         solves_per_s = args.steps / dt
@@ -561,15 +602,17 @@ def main():
         b_alg_solve = 3 * 4 * dc * N_local * T + 8 * N_local
         # dominant kernel = rollout_cost_kernel: reads the noise once, writes costs once
         b_alg_rollout = 4 * dc * N_local * T + 4 * N_local
+        # the dominant kernel's HIP-event time: inside the timed region (--timing 1 or 2) or from the per-stage pass (--full)
         t_roll = stages["rollout_cost"] * 1e-3
-        achieved = b_alg_rollout / t_roll / 1e9
-        dev_solve_ms = sum(stages[k] for k in ("sample", "rollout_cost", "weights_reduce", "finalize"))
+        achieved = b_alg_rollout / t_roll / 1e9 if t_roll > 0 else None
+        # every stage's time: --timing 1, or the per-stage pass of --full
+        dev_solve_ms = sum(stages[k] for k in ("sample", "rollout_cost", "weights_reduce", "finalize")) if best["all_stages"] else None
         # PMC counters of the dominant kernel for THIS configuration, per launch: collected with rocprofv3 --pmc in
         # separate passes over this same command and committed (profiles/pmc_constants.json names the CSV summaries
         # they were generated from by scripts/pmc_constants.py); a bench run cannot collect counters on itself.
         traffic, valu, traffic_src, traffic_stale, solve_pmc = None, None, None, None, None
         try:
-            if (N_local, T, args.math) == (1 << 20, 50, 2):
+            if achieved is not None and (N_local, T, args.math) == (1 << 20, 50, 2):
                 from mppi_playground_amd import _build
 
                 pc = json.load(open(os.path.join(ROOT, "profiles", "pmc_constants.json")))
@@ -587,7 +630,7 @@ def main():
                         "counters_stale": traffic_stale,
                         "note": "wave64 VALU instructions (SQ_INSTS_VALU, rocprofv3) / live kernel time"}
                 ks = pc.get("solve_regen" if args.noise_regen else "solve_tiles")
-                if ks and ks.get("fetch_kb") is not None:
+                if ks and ks.get("fetch_kb") is not None and dev_solve_ms:
                     solve_pmc = {"bytes_moved": int((2 * ks["fetch_kb"] + ks["write_kb"]) * 1024),
                                  "valu_insts": ks.get("valu_insts"),
                                  "valu_frac": None if not ks.get("valu_insts") else ks["valu_insts"] / (dev_solve_ms * 1e-3) / peak}
@@ -610,43 +653,45 @@ def main():
                        "exchange_used": used, "exchange_requested": args.exchange if world > 1 else None,
                        "backend": backend, "ranks_share_one_device": one_device and world > 1},
             "solves_per_sec": solves_per_s,
+        }
+        if achieved is not None:
             # the kernel is VALU-issue bound (valu_roofline), not HBM bound: `achieved`/`frac` price its ALGORITHMIC
             # bytes (the noise it consumes is regenerated in registers, so `traffic` is ~1 % of them) against the
             # HBM peak, as the metric asks; they cannot exceed ~0.45 at this instruction count
-            "roofline": {"bound": "valu", "kernel": "rollout_cost_kernel<racing>", "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale,
-                         "algorithmic_bytes_per_launch": b_alg_rollout, "kernel_ms": stages["rollout_cost"],
-                         # what the kernel really moves (PMC bytes / its time) and how much of the VALU issue peak it uses:
-                         # read `frac` next to these two
-                         "hbm_measured_GBps": None if traffic is None else traffic / t_roll / 1e9,
-                         "valu_frac": None if valu is None else valu["frac"],
-                         "note": "`achieved` / `frac` price the kernel's ALGORITHMIC bytes (SURVEY 8d: the noise it consumes + the "
-                                 "costs it writes) against the HBM peak as the metric asks; the kernel regenerates that noise in "
-                                 "registers, moves ~1 %% of those bytes (`hbm_measured_GBps`) and is bound by VALU issue "
-                                 "(`valu_frac`; 0.69 is what its instruction mix allows).  Whole solve: SURVEY 8d's B_alg / "
-                                 "ms_per_step = %.2f x the HBM peak — not a bandwidth: two of B_alg's three noise-sized terms never "
-                                 "exist (no sampler pass, no second read) and at lambda = 1 the weighted reduction is an arg-min "
-                                 "over one or two of 16 384 tiles.  `other_configs.c3_dense` is the same workload with a dense "
-                                 "softmax (every tile regenerated a second time), with its own per-kernel roofline."
-                                 % (b_alg_solve / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS)},
+            out["roofline"] = {"bound": "valu", "kernel": "rollout_cost_kernel<racing>", "achieved": achieved,
+                               "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale,
+                               "algorithmic_bytes_per_launch": b_alg_rollout, "kernel_ms": stages["rollout_cost"],
+                               # what the kernel really moves (PMC bytes / its time) and how much of the VALU issue peak it uses:
+                               # read `frac` next to these two
+                               "hbm_measured_GBps": None if traffic is None else traffic / t_roll / 1e9,
+                               "valu_frac": None if valu is None else valu["frac"],
+                               "note": "`achieved` / `frac` price the kernel's ALGORITHMIC bytes (SURVEY 8d: the noise it consumes + the "
+                                       "costs it writes) against the HBM peak as the metric asks; the kernel regenerates that noise in "
+                                       "registers, moves ~1 %% of those bytes (`hbm_measured_GBps`) and is bound by VALU issue "
+                                       "(`valu_frac`; 0.69 is what its instruction mix allows).  Whole solve: SURVEY 8d's B_alg / "
+                                       "ms_per_step = %.2f x the HBM peak — not a bandwidth: two of B_alg's three noise-sized terms never "
+                                       "exist (no sampler pass, no second read) and at lambda = 1 the weighted reduction is an arg-min "
+                                       "over one or two of 16 384 tiles.  `other_configs.c3_dense` is the same workload with a dense "
+                                       "softmax (every tile regenerated a second time), with its own per-kernel roofline."
+                                       % (b_alg_solve / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS)}
+        if dev_solve_ms is not None:
             # the whole solve (every kernel of it): what it MOVES through HBM (PMC, all mppi:: kernels of a solve) and how
             # much of the VALU issue peak it uses over its device time.  SURVEY 8d's B_alg (three noise-sized terms + the
             # costs) is kept for reference only: two of its terms never touch HBM in this design (the noise is
             # regenerated in registers) and at lambda = 1 the third is an arg-min over one or two tiles, so
             # B_alg / time is not a bandwidth (it exceeded the 8 TB/s peak in round 3); `other_configs.c3_dense`
             # times the solve whose weighted reduction does touch every tile.
-            "solve_roofline": {"device_ms_per_solve": dev_solve_ms,
-                               "bytes_moved": None if solve_pmc is None else solve_pmc["bytes_moved"],
-                               "moved_GBps": None if solve_pmc is None else solve_pmc["bytes_moved"] / (dev_solve_ms * 1e-3) / 1e9,
-                               "valu_insts": None if solve_pmc is None else solve_pmc["valu_insts"],
-                               "valu_frac": None if solve_pmc is None else solve_pmc["valu_frac"],
-                               "counters_stale": traffic_stale,
-                               "algorithmic_bytes_per_solve_survey_8d": b_alg_solve,
-                               "note": "bytes_moved / valu_insts: rocprofv3 PMC sums over every kernel of one solve "
-                                       "(profiles/pmc_constants.json); the solve is VALU-issue bound, not HBM bound"},
-            "stages_ms": {k: stages[k] for k in ("sample", "rollout_cost", "weights_reduce", "finalize")},
-        }
+            out["solve_roofline"] = {"device_ms_per_solve": dev_solve_ms,
+                                     "bytes_moved": None if solve_pmc is None else solve_pmc["bytes_moved"],
+                                     "moved_GBps": None if solve_pmc is None else solve_pmc["bytes_moved"] / (dev_solve_ms * 1e-3) / 1e9,
+                                     "valu_insts": None if solve_pmc is None else solve_pmc["valu_insts"],
+                                     "valu_frac": None if solve_pmc is None else solve_pmc["valu_frac"],
+                                     "counters_stale": traffic_stale,
+                                     "algorithmic_bytes_per_solve_survey_8d": b_alg_solve,
+                                     "note": "bytes_moved / valu_insts: rocprofv3 PMC sums over every kernel of one solve "
+                                             "(profiles/pmc_constants.json); the solve is VALU-issue bound, not HBM bound"}
+            out["stages_ms"] = {k: stages[k] for k in ("sample", "rollout_cost", "weights_reduce", "finalize")}
         out["config"]["state_seq"] = ("opt-in lazy_state_seq=True: solve k's batch-1 rollout rides in an extra block of solve k+1's "
                                       "rollout launch; the last one is completed inside the timed region" if solver._lazy_state else
                                       "default: rolled out inside the solve's last kernel")
@@ -687,9 +732,11 @@ def main():
     if world == 1:
         runs = [timed_run(None)]
         assert "error" not in runs[0] and runs[0]["finite"]
+        if args.dump_outputs:
+            write_outputs(dump_dir(args), runs[0]["outputs"])
         out = compose(runs[0], runs)
         ctrl = runs[0]["ctrl"]
-        if args.steps < 200:
+        if args.full and args.steps < 200:
             # the same solver, the same instrumentation (--timing), over 200 steps, three times: a timed region has a fixed cost
             # (pipeline fill after the synchronise, the final wake-up), so the per-step time of a longer region must not
             # be ABOVE the contract's K-step one.  Round 5's driver line had 0.1450 against 0.1403; reproduced in round 6: a
@@ -724,7 +771,7 @@ def main():
                                "ratio_to_headline": b["ms_per_step"] / (runs[0]["dt"] / args.steps * 1e3),
                                "note": "best of three 200-step regions on the headline's solver (every repetition listed); the "
                                        "contract's line above times ONE region of --steps %d" % args.steps}
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             # the opt-in lazily completed state sequence (the headline is the solver's default: completed inside finalize_kernel)
             er = timed_run(None, lazy=not bool(args.lazy_state_seq))
             out["lazy_state_seq_opt_in" if not args.lazy_state_seq else "default_state_seq"] = {
@@ -737,7 +784,7 @@ def main():
             out["closed_loop"] = closed_loop(torch, env, ctrl, T, N_total)
             out["example_loop"] = example_loop(torch)
             out["other_configs"] = other_configs(torch, np)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(np, T, ref_holder["ref"].numpy(), x0.cpu().numpy())
             runs[0]["ctrl"] = None
             del ctrl
@@ -763,21 +810,25 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
         sys.exit(1)
-    # strong-scaling leg (BASELINE's metric also reads "racing N = 1M ... at 1/2/4/8 GPUs"): the SAME 2^20 samples split
-    # over the ranks, on the transport that won the weak leg, behind the same watchdog.  Reported next to the weak-scaling
-    # `value` (which stays the contract's line: fixed work per GPU), never instead of it.
-    dog.arm(args.alt_budget_s, "strong-scaling leg")
-    sr = timed_run(best["requested"], n_total=N_local)
-    dog.cancel()
-    if "error" in sr or not sr["finite"]:
-        extras["strong"] = {"error": sr.get("error", "non-finite outputs")}
-    else:
-        extras["strong"] = {"scaling": "strong", "num_samples_total": N_local, "num_samples_per_gpu": N_local // world,
-                            "exchange": sr["exchange"], "ms_per_step": sr["dt"] / args.steps * 1e3,
-                            "solves_per_sec": args.steps / sr["dt"], "value": N_local * T * args.steps / sr["dt"],
-                            "unit": "sample-steps/s", "exchange_us": None if sr["exchange_ms"] is None else sr["exchange_ms"] * 1e3,
-                            "per_rank_stages_ms": sr["rank_stages"]}
-    sr["ctrl"] = None
+    if rank == 0 and args.dump_outputs:
+        write_outputs(dump_dir(args), best["outputs"])
+    # strong-scaling leg (--full; BASELINE's metric also reads "racing N = 1M ... at 1/2/4/8 GPUs"): the SAME 2^20 samples
+    # split over the ranks, on the transport that won the weak leg, behind the same watchdog.  Reported next to the
+    # weak-scaling `value` (which stays the contract's line: fixed work per GPU), never instead of it.
+    if args.full:
+        dog.arm(args.alt_budget_s, "strong-scaling leg")
+        sr = timed_run(best["requested"], n_total=N_local)
+        dog.cancel()
+        if "error" in sr or not sr["finite"]:
+            extras["strong"] = {"error": sr.get("error", "non-finite outputs")}
+        else:
+            extras["strong"] = {"scaling": "strong", "num_samples_total": N_local, "num_samples_per_gpu": N_local // world,
+                                "exchange": sr["exchange"], "ms_per_step": sr["dt"] / args.steps * 1e3,
+                                "solves_per_sec": args.steps / sr["dt"], "value": N_local * T * args.steps / sr["dt"],
+                                "unit": "sample-steps/s",
+                                "exchange_us": None if sr["exchange_ms"] is None else sr["exchange_ms"] * 1e3,
+                                "per_rank_stages_ms": sr["rank_stages"]}
+        sr["ctrl"] = None
     if rank == 0:
         emit(compose(best, runs))
     dog.arm(60.0, "process-group tear-down")

@@ -3,7 +3,7 @@
 # process of its own — with tight budgets, then the in-process path.  Usage: bash scripts/dry_runs.sh [ranks ...]  (default: 2)
 mkdir -p gpurun_out
 for n in ${@:-2}; do
-  MPPI_BENCH_ONE_DEVICE=1 MPPI_BENCH_BACKEND=gloo timeout 420 python bench.py --gpus $n --steps 20 --warmup 5 --first-budget-s 120 \
+  MPPI_BENCH_ONE_DEVICE=1 MPPI_BENCH_BACKEND=gloo timeout 420 python bench.py --full --gpus $n --steps 20 --warmup 5 --first-budget-s 120 \
     > gpurun_out/dry_iso_g$n.log 2> gpurun_out/dry_iso_g$n.err
   echo "dry run --gpus $n (one process per transport): rc=$?"
   python - <<PY

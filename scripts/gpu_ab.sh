@@ -3,7 +3,7 @@
 mkdir -p gpurun_out
 for rep in 1 2 3; do
 for lib in "" "$@"; do
-  MPPI_HIP_LIB=${lib:+$PWD/$lib} timeout 300 python bench.py --steps 300 --warmup 30 --no-cpu-baseline --timing 2 ${BENCH_ARGS:-} 2>/dev/null | python -c "
+  MPPI_HIP_LIB=${lib:+$PWD/$lib} timeout 300 python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline --timing 2 ${BENCH_ARGS:-} 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

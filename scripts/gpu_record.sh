@@ -8,17 +8,19 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 P=$R/gpurun_out/prof_$TAG
+OUT=$(dirname "$P")  # the record's folder: the bench lines below are read from there by make_visit_docs.py
 rm -rf $P
 timeout 1200 python -m pytest tests -m gpu -q -rfs -p no:cacheprovider 2>&1 | tail -60 > gpurun_out/pytest_gpu.log; tail -4 gpurun_out/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; tail -1 gpurun_out/smoke.log
-timeout 900 python bench.py > gpurun_out/bench.log 2>&1; tail -c 600 gpurun_out/bench.log; echo
-timeout 300 python bench.py --steps 100 --warmup 20 --noise-regen 0 --no-cpu-baseline --no-extras > gpurun_out/bench_tiles.log 2>&1
+timeout 900 python bench.py --full > "$OUT/bench.log" 2>&1; tail -c 600 "$OUT/bench.log"; echo
+timeout 300 python bench.py --full --steps 100 --warmup 20 --noise-regen 0 --no-cpu-baseline --no-extras > "$OUT/bench_tiles.log" 2>&1
 # the N > 1 path on this one GPU: ranks share the device, gloo instead of RCCL (RCCL needs one device per rank)
 # ("all" times every transport with the full K steps and reports the best complete run; RCCL cannot put two ranks on one
 # device, so the in-library communicator shows up as an error entry under `transports` here)
 for spec in "2 all" "2 nccl" "8 all"; do
   set -- $spec
-  MPPI_BENCH_ONE_DEVICE=1 MPPI_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus $1 --exchange $2 --steps 20 --warmup 5 > gpurun_out/bench_dry_g$1_$2.log 2>&1
+  MPPI_BENCH_ONE_DEVICE=1 MPPI_BENCH_BACKEND=gloo timeout 600 python bench.py --full --gpus $1 --exchange $2 --steps 20 --warmup 5 \
+    > "$OUT/bench_dry_g$1_$2.log" 2>&1
   echo "dry run --gpus $1 --exchange $2: rc=$? $(tail -1 gpurun_out/bench_dry_g$1_$2.log | cut -c1-160)"
 done
 # --preflight of the N > 1 path (process group, every transport's self-test, one sharded solve each) on this one GPU

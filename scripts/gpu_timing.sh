@@ -1,6 +1,6 @@
 #!/bin/bash
 for t in 2; do
-timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --timing $t 2>/dev/null | python -c "
+timeout 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --timing $t 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -17,6 +17,8 @@ Usage (container only; the GPU box has no /root/reference):
                                                   # BASELINE.json's configs at FULL size through the real reference,
                                                   # seed 42, two closed-loop solves; outputs and summaries only (< 100 KB)
     python tests/golden/make_golden.py only <substring> [...]   # the small cases whose name contains a substring
+    python tests/golden/make_golden.py closures   # the classic-control examples' own closures as pi_mpc.recognize sees them:
+                                                  # their fingerprints (sha256) and their values on its probe batches
 
 Recipe follows SURVEY.md Appendix C: stub the UI-only imports (moviepy, fire,
 gymnasium), run with cwd=/root/reference (racing_env.py:47-49 opens a relative CSV),
@@ -236,7 +238,7 @@ def _feed_solve(solver, rec, state, costs):
 
 
 MODE = sys.argv[1] if len(sys.argv) > 1 else "all"
-assert MODE in ("all", "round2", "round5", "fullsize", "only"), MODE
+assert MODE in ("all", "round2", "round5", "fullsize", "only", "closures"), MODE
 ONLY_ROUND2 = MODE == "round2"
 PARTIAL = MODE != "all"  # env artefacts, RNG stream and model pins are rewritten by the full run only
 ROUND2 = set()  # names registered with round2=True
@@ -824,5 +826,63 @@ def main():
     print("done")
 
 
+def _example_closures(model):
+    """(dynamics, cost) as example/<model>.py holds them — nested definitions inside main(), `dynamics` a TorchScript function,
+    the cost a closure over the module-level TorchScript angle_normalize — rebuilt from the reference's file in a scratch
+    module outside the repository."""
+    import importlib.util
+    import tempfile
+
+    fn, dyn_name, cost_name = {"pendulum": ("pendulum.py", "dynamics", "cost_function"),
+                               "cartpole": ("cartpole.py", "dynamics", "stage_cost"),
+                               "mountaincar": ("mountaincar.py", "dynamics", "cost_func"),
+                               "mjcartpole": ("mujoco_cartpole.py", "dynamics", "cost_func")}[model]
+    tree = ast.parse(open(os.path.join(REF, "example", fn)).read())
+    body = ["import torch\n"]
+    for node in tree.body:
+        if isinstance(node, ast.FunctionDef) and node.name == "angle_normalize":
+            body.append(ast.unparse(node) + "\n")
+    main_fn = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "main"][0]
+    inner = [textwrap.indent(textwrap.dedent(ast.unparse(n)), "    ") for n in main_fn.body
+             if isinstance(n, ast.FunctionDef) and n.name in (dyn_name, cost_name)]
+    body.append("def main():\n" + "\n".join(inner) + f"\n    return {dyn_name}, {cost_name}\n")  # nested, like the example
+    path = os.path.join(tempfile.mkdtemp(prefix="mppi_ref_example_"), f"ref_example_{model}.py")
+    open(path, "w").write("\n".join(body))
+    spec = importlib.util.spec_from_file_location(f"ref_example_{model}", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.main()
+
+
+def record_closures():
+    """reference_example_closures.npz: per classic-control model, what pi_mpc.recognize reads from the reference example's
+    (dynamics, cost) — every form of their fingerprint (sha256 hex digests), whether each is a TorchScript function, and their
+    values on recognize's probe batches (dynamics: what it returns and what it leaves in its state argument).  Hashes and
+    arrays only."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    import torch
+
+    import mppi_playground_amd  # noqa: F401  (puts pi_mpc/ and envs/ on sys.path)
+    from pi_mpc import recognize
+
+    cpu = torch.device("cpu")
+    rec = {"torch": np.array(torch.__version__)}
+    for model in ("pendulum", "cartpole", "mountaincar", "mjcartpole"):
+        dyn, cost = _example_closures(model)
+        s, a = recognize._probes(model, cpu)
+        s1 = s.clone()
+        out = dyn(s1, a.clone())
+        info = {"t": 0, "prev_state": s, "prev_action": a, "initial_state": s}
+        rec[f"{model}_dyn_fp"] = np.array(sorted(recognize.fingerprints(dyn)))
+        rec[f"{model}_cost_fp"] = np.array(sorted(recognize.fingerprints(cost)))
+        rec[f"{model}_dyn_is_script"] = np.array(isinstance(dyn, torch.jit.ScriptFunction))
+        rec[f"{model}_cost_is_script"] = np.array(isinstance(cost, torch.jit.ScriptFunction))
+        rec[f"{model}_dyn_out"] = out.numpy().copy()
+        rec[f"{model}_dyn_arg"] = s1.numpy().copy()
+        rec[f"{model}_cost_out"] = cost(s.clone(), a.clone(), dict(info)).numpy().copy()
+    np.savez_compressed(os.path.join(OUT, "reference_example_closures.npz"), **rec)
+    print("wrote reference_example_closures.npz")
+
+
 if __name__ == "__main__":
-    main()
+    record_closures() if MODE == "closures" else main()

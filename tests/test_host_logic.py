@@ -465,6 +465,31 @@ def test_bench_runs_every_transport_in_its_own_process(monkeypatch, capsys):
     assert out["value"] is None and out["n_gpus"] == 8 and len(out["transports"]) == 2
 
 
+def test_bench_dump_outputs_of_the_best_transport(monkeypatch, tmp_path):
+    """`--dump-outputs DIR` with one process per transport: each transport's process writes DIR/<transport>/ (bench.dump_dir
+    reads MPPI_BENCH_CHILD) and the parent copies the best complete transport's arrays up into DIR."""
+    import argparse
+    import importlib
+    import json
+
+    bench = importlib.import_module("bench")
+    args = argparse.Namespace(steps=20, warmup=5, samples=1 << 20, horizon=50, first_budget_s=300.0, dump_outputs=str(tmp_path))
+    monkeypatch.setattr(bench, "print_line", lambda text: None)
+
+    def run_child(mode, index, budget_s):
+        monkeypatch.setenv("MPPI_BENCH_CHILD", mode)
+        bench.write_outputs(bench.dump_dir(args), {"action_seq": np.full((3, 2), index, np.float64)})
+        monkeypatch.delenv("MPPI_BENCH_CHILD")
+        line = {"value": [1.0, 3.0, 2.0][index], "ms_per_step": 0.1, "config": {"exchange_used": mode}}
+        return 0, json.dumps(line) + "\n", 1.0
+
+    assert bench.dump_dir(args) == str(tmp_path)
+    assert bench.orchestrate_transports(args, 2, 0, ["rccl", "nccl", "p2p"], run_child=run_child) == 0
+    got = np.load(tmp_path / "action_seq.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, np.ones((3, 2), np.float32))  # nccl's: the best value
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["action_seq.npy", "nccl", "p2p", "rccl"]
+
+
 def test_lbps_grid_search_finds_the_brent_minimum_on_random_costs():
     """The grid variant of the LBPS search against scipy's bounded Brent minimiser (the reference's call) on a float64
     evaluation of the objective, over cost vectors of different shapes; where Brent stops in a local minimum the grid may
@@ -656,52 +681,49 @@ def test_bench_stdout_carries_only_its_line():
 
 
 # ------------------------------------------------------------------------------ the reference examples' own closures
-def _reference_example_closures(model):
-    """(dynamics, cost) as example/<model>.py holds them — nested definitions inside main(), `dynamics` a TorchScript function,
-    the cost a closure over the module-level TorchScript angle_normalize — rebuilt from the reference's file in a scratch
-    module (build container only; nothing is copied into the repo)."""
-    import ast
-    import importlib.util
-    import tempfile
-    import textwrap
+def _recorded_example_closures(model, monkeypatch):
+    """(dynamics, cost) standing in for example/<model>.py's own closures as pi_mpc.recognize sees them, replayed from
+    tests/golden/reference_example_closures.npz (tests/golden/make_golden.py closures): their fingerprints, and their values on
+    the recognizer's probe batches — on any other input they raise, i.e. they are not the model there."""
+    import torch
 
-    fn, dyn_name, cost_name = {"pendulum": ("pendulum.py", "dynamics", "cost_function"),
-                               "cartpole": ("cartpole.py", "dynamics", "stage_cost"),
-                               "mountaincar": ("mountaincar.py", "dynamics", "cost_func"),
-                               "mjcartpole": ("mujoco_cartpole.py", "dynamics", "cost_func")}[model]
-    tree = ast.parse(open(os.path.join("/root/reference/example", fn)).read())
-    body = ["import torch\n"]
-    for node in tree.body:
-        if isinstance(node, ast.FunctionDef) and node.name == "angle_normalize":
-            body.append(ast.unparse(node) + "\n")
-    main = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "main"][0]
-    inner = [textwrap.indent(textwrap.dedent(ast.unparse(n)), "    ") for n in main.body
-             if isinstance(n, ast.FunctionDef) and n.name in (dyn_name, cost_name)]
-    body.append("def main():\n" + "\n".join(inner) + f"\n    return {dyn_name}, {cost_name}\n")  # nested, like the example
-    d = tempfile.mkdtemp(prefix="mppi_ref_example_")
-    path = os.path.join(d, f"ref_example_{model}.py")
-    open(path, "w").write("\n".join(body))
-    spec = importlib.util.spec_from_file_location(f"ref_example_{model}", path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.main()
+    from pi_mpc import recognize
+
+    g = np.load(os.path.join(ROOT, "tests", "golden", "reference_example_closures.npz"))
+    s0, a0 = recognize._probes(model, torch.device("cpu"))
+
+    def on_probes(s, a):
+        if not (s.shape == s0.shape and a.shape == a0.shape and torch.equal(s, s0) and torch.equal(a, a0)):
+            raise ValueError("recorded on the probe batches only")
+
+    def dyn(s, a):
+        on_probes(s, a)
+        s.copy_(torch.from_numpy(g[f"{model}_dyn_arg"]))  # (what the call leaves in its argument)
+        return torch.from_numpy(g[f"{model}_dyn_out"].copy())
+
+    def cost(s, a, info):
+        on_probes(s, a)
+        return torch.from_numpy(g[f"{model}_cost_out"].copy())
+
+    recorded = {dyn: set(g[f"{model}_dyn_fp"].tolist()), cost: set(g[f"{model}_cost_fp"].tolist())}
+    computed = recognize.fingerprints
+    monkeypatch.setattr(recognize, "fingerprints", lambda fn: recorded[fn] if fn in recorded else computed(fn))
+    return dyn, cost, bool(g[f"{model}_dyn_is_script"]), bool(g[f"{model}_cost_is_script"])
 
 
 @pytest.mark.parametrize("model", ["pendulum", "cartpole", "mountaincar", "mjcartpole"])
-def test_reference_example_closures_are_recognised(model):
-    """pi_mpc/recognize.py on the REAL closures of the reference's classic-control examples (container only): the committed
-    fingerprints match what the installed torch prints for them, the shipped torch plugin of that model agrees with them on the
-    probe batches (values returned AND — mountain car — what the call leaves in its argument), and an edited copy is not
+def test_reference_example_closures_are_recognised(model, monkeypatch):
+    """pi_mpc/recognize.py on the REAL closures of the reference's classic-control examples, as recorded from them: the
+    committed fingerprints match what torch printed for them, the shipped torch plugin of that model agrees with their values on
+    the probe batches (values returned AND — mountain car — what the call leaves in its argument), and an edited copy is not
     recognised."""
-    if not os.path.isdir("/root/reference/example"):
-        pytest.skip("needs the reference's example files (build container)")
     import torch
 
     from envs import classic_control as cc
     from pi_mpc import recognize
 
-    dyn, cost = _reference_example_closures(model)
-    assert isinstance(dyn, torch.jit.ScriptFunction) and not isinstance(cost, torch.jit.ScriptFunction)
+    dyn, cost, dyn_is_script, cost_is_script = _recorded_example_closures(model, monkeypatch)
+    assert dyn_is_script and not cost_is_script
     ds, dc = recognize._MODELS[model][:2]
     twin = recognize.match(dyn, cost, ds, dc, torch.device("cpu"))
     assert twin == (getattr(cc, f"{model}_dynamics"), getattr(cc, f"{model}_cost"))
