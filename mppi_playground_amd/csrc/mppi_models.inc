@@ -45,6 +45,11 @@ MPPI_HD float angle_normalize(float x, bool& bad) {
 // bounded below pi (ctx.wrap_safe), so fl(x + pi) lies in (-pi, 3pi): one conditional subtraction and
 // the sign fix remain (wrap_inc_f).  Both are bit-identical to the library path on those ranges; the
 // initial state is range-checked once per trajectory (Model::check_state).
+// wrap_inc_f picks the multiple of 2pi without branches: k = floor(fl(a * RN(1/2pi_f))) is -1 for a < 0, 0 on [0, 2pi_f)
+// and 1 on [2pi_f, 4pi_f) (RN(1/2pi_f) is the one float for which fl(2pi_f * c) = 1 and fl(pred(2pi_f) * c) < 1), and
+// fma(-k, 2pi, a) is the subtraction / addition of the branchy form rounded once, as before (k = 0: a + -0 = a, a != -0).
+// Five VALU instead of eight (add, mul, floor, fma, sub); equal to the branchy form for EVERY float x in [-2pi, 2pi]
+// (scripts/enum/enum_wrap_index.cpp, profiles/r07_enum_wrap_index.txt).
 // rewrap_f is idempotent on the outputs of both wraps: for EVERY float r in [0, 2pi] (the 1 086 918 620 of them,
 // checked exhaustively: tests/test_model_functors_host.py samples the same statement), t = fl(r - pi) satisfies
 // fl(fl(t + pi) - pi) == t.  So once the heading has been through one wrap, the entry wrap of every later step is the
@@ -52,10 +57,8 @@ MPPI_HD float angle_normalize(float x, bool& bad) {
 MPPI_HD float rewrap_f(float x) { return (x + PI_F) - PI_F; }
 MPPI_HD float wrap_inc_f(float x) {
     const float a = x + PI_F;
-    float r = a;
-    if (a >= TWO_PI_F) r = a - TWO_PI_F;
-    if (r < 0.0f) r += TWO_PI_F;  // r == -0.0f stays, like the reference's (r != 0 && r < 0)
-    return r - PI_F;
+    const float k = floorf(a * 0.159154937f);  // RN(1 / TWO_PI_F)
+    return fmaf(-k, TWO_PI_F, a) - PI_F;
 }
 
 // x with its sign flipped when bit 31 of `m` is set
