@@ -1,0 +1,298 @@
+// capi_model.hip — C ABI (include/mppi_hip.h): model parameters, maps, the reference and its device-resident window,
+// env.step and grid lookups on the device.
+#include "mppi_handle.hpp"
+#include "mppi_env.hpp"
+#include "mppi_maps.hpp"
+
+namespace mppi {
+
+// (Re)build the padded grid of the FAST lookup when the maps and the model parameters allow it; otherwise
+// ctx.pad stays null and the FAST=false kernels (bounds-tested lookups) are dispatched.
+void refresh_pad(mppi_handle_t h, hipStream_t s) {
+    h->model.ctx.pad = nullptr;
+    h->model.ctx.pad_stride = 0;
+    const int model = h->cfg.model;
+    const bool racing = model == MPPI_MODEL_RACING;
+    if (!racing && model != MPPI_MODEL_NAV2D) return;
+    if (!h->model.params_set || !h->model.map_cells[0] || (racing && !h->model.map_cells[1])) return;
+    const MapView &a = h->model.ctx.maps[0], &b = h->model.ctx.maps[1];
+    if (racing && (a.nx != b.nx || a.ny != b.ny || a.cell != b.cell || a.ox != b.ox || a.oy != b.oy)) return;
+    const float* P = h->model.ctx.P;
+    const float xlo = P[racing ? MPPI_RP_XLO : MPPI_NP_XLO], xhi = P[racing ? MPPI_RP_XHI : MPPI_NP_XHI];
+    const float ylo = P[racing ? MPPI_RP_YLO : MPPI_NP_YLO], yhi = P[racing ? MPPI_RP_YHI : MPPI_NP_YHI];
+    uint32_t koff = 0;
+    if (!pad_map_plan(a, xlo, xhi, ylo, yhi, koff)) return;
+    const size_t n = (size_t)(a.nx + 1) * (a.ny + 1);
+    if (h->model.map_pad.n < n && h->model.map_pad.alloc(n) != hipSuccess) return;
+    hipLaunchKernelGGL(pad_map_kernel, dim3((unsigned)((a.ny + 1 + BLOCK - 1) / BLOCK), (unsigned)(a.nx + 1)), dim3(BLOCK), 0, s,
+                       h->model.map_cells[0], racing ? h->model.map_cells[1] : (const uint8_t*)nullptr, a.nx, a.ny,
+                       (uint8_t)(racing ? 2 : 1), h->model.map_pad);
+    if (hipGetLastError() != hipSuccess) return;
+    h->model.ctx.pad = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(h->model.map_pad.p) - (uintptr_t)koff);
+    h->model.ctx.pad_stride = a.ny + 1;
+}
+
+// (re)allocate the grid of `slot` and fill in its geometry
+int prepare_map(mppi_handle_t h, int slot, int nx, int ny, float cell, float ox, float oy) {
+    if (!h || slot < 0 || slot > 1 || nx < 1 || ny < 1 || !(cell > 0.0f)) return fail(h, MPPI_E_INVALID, "bad map");
+    const size_t n = (size_t)nx * ny;
+    if (h->model.map_cells[slot].n < n) HIP_TRY(h, h->model.map_cells[slot].alloc(n));
+    MapView& m = h->model.ctx.maps[slot];
+    m.cells = h->model.map_cells[slot];
+    m.nx = nx; m.ny = ny; m.cell = cell; m.ox = ox; m.oy = oy;
+    // Markstein division needs y = RN(1/cell) and a significand of cell that is not all ones.
+    uint32_t bits; std::memcpy(&bits, &cell, 4);
+    const bool all_ones = (bits & 0x7fffffu) == 0x7fffffu;
+    m.inv_cell = all_ones ? 0.0f : 1.0f / cell;  // host IEEE division: correctly rounded
+    return MPPI_OK;
+}
+
+// small integer table host -> device (map recipes); blocking, setup path only
+static int upload_ints(mppi_handle_t h, const int32_t* src, size_t count, DevBuf<int32_t>& dst) {
+    if (!count) return MPPI_OK;
+    HIP_TRY(h, dst.alloc(count));
+    HIP_TRY(h, hipMemcpy(dst, src, sizeof(int32_t) * count, hipMemcpyHostToDevice));
+    return MPPI_OK;
+}
+
+// make sure h->model.ref holds `rows` rows (blocking reallocation: set-up path)
+int reserve_ref(mppi_handle_t h, int rows) {
+    if ((size_t)rows * 8 <= h->model.ref.n) return MPPI_OK;
+    if (h->model.ref) HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, h->model.ref.alloc(8 * (size_t)rows));
+    return MPPI_OK;
+}
+
+}  // namespace mppi
+
+extern "C" {
+
+int mppi_set_model_params(mppi_handle_t h, const float* p, int n) {
+    if (!h || n < 0 || n > MPPI_MAX_PARAMS || (n > 0 && !p)) return fail(h, MPPI_E_INVALID, "bad params");
+    if (n != model_param_count(h->cfg.model)) return fail(h, MPPI_E_INVALID, "parameter count does not match the model");
+    if (int rc = settle_state_seq(h)) return rc;  // a lazily completed state sequence belongs to the OLD constants: roll it out first
+    for (int i = 0; i < n; ++i) h->model.ctx.P[i] = p[i];
+    const float* um = h->cfg.u_min; const float* uM = h->cfg.u_max;
+    if (h->cfg.model == MPPI_MODEL_GOALZONE) {
+        h->model.ctx.u_in_bounds = (um[0] >= p[MPPI_GP_VMIN] && uM[0] <= p[MPPI_GP_VMAX] && um[1] >= p[MPPI_GP_WMIN] &&
+                              uM[1] <= p[MPPI_GP_WMAX]) ? 1 : 0;
+        const float w = std::fmax(std::fabs(p[MPPI_GP_WMIN]), std::fabs(p[MPPI_GP_WMAX]));
+        h->model.ctx.wrap_safe = (w * std::fabs(p[MPPI_GP_DT]) < 3.0f) ? 1 : 0;
+    }
+    if (h->cfg.model == MPPI_MODEL_NAV2D) {
+        h->model.ctx.u_in_bounds = (um[0] >= p[MPPI_NP_VMIN] && uM[0] <= p[MPPI_NP_VMAX] && um[1] >= p[MPPI_NP_WMIN] &&
+                              uM[1] <= p[MPPI_NP_WMAX]) ? 1 : 0;
+        const float w = std::fmax(std::fabs(p[MPPI_NP_WMIN]), std::fabs(p[MPPI_NP_WMAX]));
+        h->model.ctx.wrap_safe = (w * std::fabs(p[MPPI_NP_DT]) < 3.0f) ? 1 : 0;
+    }
+    if (h->cfg.model == MPPI_MODEL_RACING) {
+        h->model.ctx.u_in_bounds = (um[0] >= p[MPPI_RP_AMIN] && uM[0] <= p[MPPI_RP_AMAX] && um[1] >= p[MPPI_RP_SMIN] &&
+                              uM[1] <= p[MPPI_RP_SMAX]) ? 1 : 0;
+        const float sm = std::fmax(std::fabs(p[MPPI_RP_SMIN]), std::fabs(p[MPPI_RP_SMAX]));
+        const float dth = std::fabs(p[MPPI_RP_VMAX]) * std::tan(std::fmin(sm, 1.5f)) / std::fabs(p[MPPI_RP_L]) *
+                          std::fabs(p[MPPI_RP_DT]);
+        h->model.ctx.wrap_safe = (sm < 1.5f && dth < 3.0f) ? 1 : 0;
+        h->model.ctx.tan_small = (std::fabs(p[MPPI_RP_SMIN]) <= 0.25f && std::fabs(p[MPPI_RP_SMAX]) <= 0.25f) ? 1 : 0;
+        const float L = p[MPPI_RP_L];
+        uint32_t bits; std::memcpy(&bits, &L, 4);
+        h->model.ctx.inv_L = (L > 0.0f && (bits & 0x7fffffu) != 0x7fffffu) ? 1.0f / L : 0.0f;
+        h->model.ctx.unit_L = L == 1.0f ? 1 : 0;
+    }
+    h->model.params_set = true;
+    refresh_pad(h, nullptr);  // the padded grid depends on the position clamp limits
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(h, MPPI_E_HIP, "padded grid construction failed");
+    return MPPI_OK;
+}
+
+int mppi_upload_map(mppi_handle_t h, int slot, const uint8_t* cells, int nx, int ny, float cell, float ox, float oy) {
+    if (!h || !cells) return fail(h, MPPI_E_INVALID, "bad map");
+    const size_t n = (size_t)(nx > 0 ? nx : 0) * (ny > 0 ? ny : 0);
+    for (size_t i = 0; i < n; ++i)
+        if (cells[i] > 1) return fail(h, MPPI_E_INVALID, "map cells must be 0/1 occupancy");
+    if (int rc = settle_state_seq(h)) return rc;  // (a pending state sequence keeps the kernel variant of ITS solve)
+    if (int rc = prepare_map(h, slot, nx, ny, cell, ox, oy)) return rc;
+    HIP_TRY(h, hipMemcpy(h->model.map_cells[slot], cells, n, hipMemcpyHostToDevice));
+    refresh_pad(h, nullptr);
+    HIP_TRY(h, hipStreamSynchronize(nullptr));
+    return MPPI_OK;
+}
+
+int mppi_build_obstacle_map(mppi_handle_t h, int slot, int nx, int ny, float cell, float ox, float oy,
+                            const int32_t* circles, int n_circles, const int32_t* rects, int n_rects, void* stream) {
+    if (!h || n_circles < 0 || n_rects < 0 || (n_circles && !circles) || (n_rects && !rects))
+        return fail(h, MPPI_E_INVALID, "bad obstacle list");
+    for (int c = 0; c < n_circles; ++c)
+        if (circles[3 * c + 2] < 0) return fail(h, MPPI_E_INVALID, "circle radius must be >= 0 cells");
+    if (int rc = settle_state_seq(h)) return rc;  // (a pending state sequence keeps the kernel variant of ITS solve)
+    if (int rc = prepare_map(h, slot, nx, ny, cell, ox, oy)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf<int32_t> dc, dr;  // (the recipe tables, freed on return)
+    if (int rc = upload_ints(h, circles, (size_t)3 * n_circles, dc)) return rc;
+    if (int rc = upload_ints(h, rects, (size_t)4 * n_rects, dr)) return rc;
+    hipLaunchKernelGGL(mppi::raster_obstacles_kernel, dim3((ny + mppi::BLOCK - 1) / mppi::BLOCK, nx), dim3(mppi::BLOCK), 0,
+                       s, h->model.map_cells[slot].p, nx, ny, dc.p, n_circles, dr.p, n_rects);
+    const hipError_t e = hipGetLastError();
+    refresh_pad(h, s);
+    const hipError_t e2 = hipStreamSynchronize(s);  // (before the recipe tables are freed)
+    HIP_TRY(h, e);
+    HIP_TRY(h, e2);
+    return MPPI_OK;
+}
+
+int mppi_build_lane_map(mppi_handle_t h, int slot, int nx, int ny, float cell, float ox, float oy,
+                        const int32_t* seeds, int n_seeds, int64_t max_d2, void* stream) {
+    if (!h || n_seeds < 1 || !seeds || max_d2 < 0) return fail(h, MPPI_E_INVALID, "bad lane seeds");
+    if (int rc = settle_state_seq(h)) return rc;  // (a pending state sequence keeps the kernel variant of ITS solve)
+    if (int rc = prepare_map(h, slot, nx, ny, cell, ox, oy)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf<int32_t> ds;  // (freed on return)
+    if (int rc = upload_ints(h, seeds, (size_t)2 * n_seeds, ds)) return rc;
+    hipLaunchKernelGGL(mppi::lane_map_kernel, dim3((ny + mppi::BLOCK - 1) / mppi::BLOCK, nx), dim3(mppi::BLOCK), 0, s,
+                       h->model.map_cells[slot].p, nx, ny, ds.p, n_seeds, max_d2);
+    const hipError_t e = hipGetLastError();
+    refresh_pad(h, s);
+    const hipError_t e2 = hipStreamSynchronize(s);  // (before the seed table is freed)
+    HIP_TRY(h, e);
+    HIP_TRY(h, e2);
+    return MPPI_OK;
+}
+
+int mppi_download_map(mppi_handle_t h, int slot, uint8_t* cells_host, int* nx, int* ny) {
+    if (!h || slot < 0 || slot > 1) return fail(h, MPPI_E_INVALID, "bad slot");
+    if (!h->model.map_cells[slot]) return fail(h, MPPI_E_STATE, "map slot is empty");
+    const MapView& m = h->model.ctx.maps[slot];
+    if (nx) *nx = m.nx;
+    if (ny) *ny = m.ny;
+    if (cells_host) {
+        HIP_TRY(h, hipDeviceSynchronize());
+        HIP_TRY(h, hipMemcpy(cells_host, h->model.map_cells[slot], (size_t)m.nx * m.ny, hipMemcpyDeviceToHost));
+    }
+    return MPPI_OK;
+}
+
+int mppi_set_reference(mppi_handle_t h, const float* ref, int rows, void* stream) {
+    if (!h || !ref || rows < 1) return fail(h, MPPI_E_INVALID, "bad reference");
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = reserve_ref(h, rows)) return rc;
+    float* st = nullptr; hipEvent_t ev = nullptr;
+    if (int rc = stage_slot(h, (size_t)rows * 8, &st, &ev)) return rc;
+    for (int i = 0; i < rows; ++i) {
+        float* o = st + (size_t)i * 8;
+        o[0] = ref[4 * i]; o[1] = ref[4 * i + 1]; o[2] = ref[4 * i + 2]; o[3] = ref[4 * i + 3];
+        o[4] = sinf(o[2]); o[5] = cosf(o[2]);  // torch.sin/cos of the fp32 scalar, racing.py:127-139
+        o[6] = o[7] = 0.0f;
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->model.ref, st, sizeof(float) * 8 * (size_t)rows, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(ev, s));
+    h->model.ctx.ref = h->model.ref;
+    h->model.ctx.ref_rows = rows;
+    return MPPI_OK;
+}
+
+int mppi_set_center_path(mppi_handle_t h, const float* path_host, int n, const int32_t* dind_host, int rows,
+                         float v_target) {
+    if (!h || !path_host || !dind_host || n < 1 || rows < 1) return fail(h, MPPI_E_INVALID, "bad centre path");
+    if (h->cfg.model != MPPI_MODEL_RACING) return fail(h, MPPI_E_INVALID, "the reference window belongs to the racing model");
+    if (rows < h->d.T) return fail(h, MPPI_E_INVALID, "window shorter than the horizon");
+    for (int i = 0; i < rows; ++i)
+        if (dind_host[i] < 0 || (i && dind_host[i] < dind_host[i - 1])) return fail(h, MPPI_E_INVALID, "window offsets must be >= 0 and non-decreasing");
+    std::vector<float> tab((size_t)n * 8, 0.0f);
+    for (int i = 0; i < n; ++i) {
+        float* o = tab.data() + (size_t)i * 8;
+        o[0] = path_host[3 * i]; o[1] = path_host[3 * i + 1]; o[2] = path_host[3 * i + 2];
+        o[4] = sinf(o[2]); o[5] = cosf(o[2]);  // the calls mppi_set_reference makes per window row
+    }
+    HIP_TRY(h, hipDeviceSynchronize());
+    h->model.center_n = 0;
+    HIP_TRY(h, h->model.center8.alloc(tab.size()));
+    HIP_TRY(h, hipMemcpy(h->model.center8, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, h->model.win_dind.alloc((size_t)rows));
+    HIP_TRY(h, hipMemcpy(h->model.win_dind, dind_host, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice));
+    if (!h->model.path_index) HIP_TRY(h, h->model.path_index.alloc_set(1, 0));
+    if (int rc = reserve_ref(h, rows)) return rc;
+    h->model.center_n = n; h->model.win_rows = rows; h->model.win_v = v_target;
+    return MPPI_OK;
+}
+
+int mppi_ref_window(mppi_handle_t h, const float* state_dev, void* stream) {
+    if (!h) return MPPI_E_INVALID;
+    if (!h->model.center_n) return fail(h, MPPI_E_STATE, "mppi_ref_window before mppi_set_center_path");
+    const RefWindowCtx w{h->model.center8, h->model.win_dind, h->model.path_index, h->model.center_n, h->model.win_rows, h->model.win_v};
+    hipLaunchKernelGGL(ref_window_kernel, dim3(1), dim3(REFWIN_BLOCK), 0, (hipStream_t)stream, w,
+                       state_dev ? state_dev : h->core.x0_cur, h->model.ref);
+    HIP_TRY(h, hipGetLastError());
+    h->model.ctx.ref = h->model.ref;
+    h->model.ctx.ref_rows = h->model.win_rows;
+    return MPPI_OK;
+}
+
+int mppi_set_path_index(mppi_handle_t h, int32_t cind, void* stream) {
+    if (!h || cind < 0) return fail(h, MPPI_E_INVALID, "bad path index");
+    if (!h->model.path_index) return fail(h, MPPI_E_STATE, "mppi_set_path_index before mppi_set_center_path");
+    HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(h, hipMemcpy(h->model.path_index, &cind, sizeof(int32_t), hipMemcpyHostToDevice));
+    return MPPI_OK;
+}
+
+int mppi_get_path_index(mppi_handle_t h, int32_t* cind_out_host, void* stream) {
+    if (!h || !cind_out_host) return fail(h, MPPI_E_INVALID, "null");
+    if (!h->model.path_index) return fail(h, MPPI_E_STATE, "mppi_get_path_index before mppi_set_center_path");
+    HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(h, hipMemcpy(cind_out_host, h->model.path_index, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MPPI_OK;
+}
+
+int mppi_get_reference(mppi_handle_t h, float* ref_out, int rows, int on_device, void* stream) {
+    if (!h || !ref_out || rows < 1) return fail(h, MPPI_E_INVALID, "bad get_reference arguments");
+    if (!h->model.ctx.ref || rows > h->model.ctx.ref_rows) return fail(h, MPPI_E_STATE, "no reference window of that many rows");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipMemcpy2DAsync(ref_out, 4 * sizeof(float), h->model.ref, 8 * sizeof(float), 4 * sizeof(float), (size_t)rows,
+                                on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    if (!on_device) HIP_TRY(h, hipStreamSynchronize(s));
+    return MPPI_OK;
+}
+
+int mppi_model_step(int model, const float* params_host, int n_params, const float* u_min_host, const float* u_max_host,
+                    const float* state_dev, const float* action_dev, float* next_state_dev, const float* goal_xy_host,
+                    float goal_threshold, uint8_t* reached_out_dev, void* stream) {
+    ModelDims md{};
+    if (!model_dims(model, md) || n_params < 0 || n_params > MPPI_MAX_PARAMS || (n_params && !params_host) ||
+        !state_dev || !action_dev || !next_state_dev || (reached_out_dev && !goal_xy_host) || md.dc > MPPI_MAX_DIM_CONTROL)
+        return MPPI_E_INVALID;
+    if (n_params < model_param_count(model)) return MPPI_E_INVALID;  // (the cost weights at the tail are not read by the dynamics)
+    ModelCtx ctx;
+    std::memset(&ctx, 0, sizeof(ctx));
+    for (int i = 0; i < n_params; ++i) ctx.P[i] = params_host[i];
+    StepBounds ub;
+    for (int k = 0; k < MPPI_MAX_DIM_CONTROL; ++k) {
+        ub.lo[k] = (u_min_host && k < md.dc) ? u_min_host[k] : -INFINITY;
+        ub.hi[k] = (u_max_host && k < md.dc) ? u_max_host[k] : INFINITY;
+    }
+    const float gx = goal_xy_host ? goal_xy_host[0] : 0.0f, gy = goal_xy_host ? goal_xy_host[1] : 0.0f;
+    hipStream_t s = (hipStream_t)stream;
+#define CALL_STEP(MODEL)                                                                              \
+    hipLaunchKernelGGL((model_step_kernel<MODEL>), dim3(1), dim3(WAVE), 0, s, ctx, state_dev, action_dev, ub,  \
+                       next_state_dev, gx, gy, goal_threshold, reached_out_dev)
+    switch (model) {
+    case MPPI_MODEL_PENDULUM: CALL_STEP(MPPI_MODEL_PENDULUM); break;
+    case MPPI_MODEL_CARTPOLE: CALL_STEP(MPPI_MODEL_CARTPOLE); break;
+    case MPPI_MODEL_MOUNTAINCAR: CALL_STEP(MPPI_MODEL_MOUNTAINCAR); break;
+    case MPPI_MODEL_NAV2D: CALL_STEP(MPPI_MODEL_NAV2D); break;
+    case MPPI_MODEL_RACING: CALL_STEP(MPPI_MODEL_RACING); break;
+    case MPPI_MODEL_MJCARTPOLE: CALL_STEP(MPPI_MODEL_MJCARTPOLE); break;
+    case MPPI_MODEL_GOALZONE: CALL_STEP(MPPI_MODEL_GOALZONE); break;
+    }
+#undef CALL_STEP
+    return hipGetLastError() == hipSuccess ? MPPI_OK : MPPI_E_HIP;
+}
+
+int mppi_grid_lookup(const float* map_dev, int nx, int ny, float cell_size, float origin_x, float origin_y, const float* xy_dev,
+                     int64_t n, int64_t stride, float* out_dev, void* stream) {
+    if (!map_dev || !xy_dev || !out_dev || nx < 1 || ny < 1 || !(cell_size > 0.0f) || n < 0 || stride < 2) return MPPI_E_INVALID;
+    if (n == 0) return MPPI_OK;
+    hipLaunchKernelGGL(grid_lookup_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, map_dev, nx,
+                       ny, cell_size, origin_x, origin_y, xy_dev, n, stride, out_dev);
+    return hipGetLastError() == hipSuccess ? MPPI_OK : MPPI_E_HIP;
+}
+
+}  // extern "C"

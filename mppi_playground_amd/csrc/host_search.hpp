@@ -1,6 +1,6 @@
 // host_search.hpp — the scalar halves of the automatic temperature rules (ESSPS / LBPS / MPO,
 // src/pi_mpc/mppi.py:341-370,387-398,526-566 of the reference), as host C++ over softmax statistics that the
-// device reduces (mppi_softmax_stats / mppi_softmax_stats_multi).  Pure C++17, no HIP: mppi_capi.hip calls
+// device reduces (mppi_softmax_stats / mppi_softmax_stats_multi).  Pure C++17, no HIP: capi_search.hip calls
 // these with device-backed statistics callbacks, tests/host_emul compiles the same header with g++ and checks
 // it against scipy / the numpy statements in pi_mpc/_host.py on a machine without a GPU.
 //
@@ -135,7 +135,7 @@ MPPI_SEARCH_HD bool lbps_lambda(S&& stats, double delta, double lam_min, double 
 // end-point rules, from two geometric grids of P temperatures (ONE pass over the costs on the device per grid) and an
 // inverse polynomial interpolation in (ESS, log lambda).  Same algorithm as pi_mpc/_host.py::essps_lambda_grid (within
 // ~1e-7 relative of scipy's brentq on the same statistics).  The search is written as three steps so that the host
-// loop below (statistics read back per grid) and the device-resident chain in mppi_kernels.hpp (essps_select_kernel:
+// loop below (statistics read back per grid) and the device-resident chain in mppi_search.hpp (essps_select_kernel:
 // no read-back at all) run the very same arithmetic.
 // point j of the geometric grid over [lo, hi] (end points exact); the device evaluates one point per lane
 template <int P>
@@ -220,7 +220,7 @@ MPPI_SEARCH_HD double essps_poly_term(const double* lgrid, const double* ess, do
     return num / den * lgrid[j0 + a];
 }
 // ... and the sum in ascending order (the device's scalar step computes the terms on NPT lanes and adds them in the same
-// order: mppi_kernels.hpp, essps_round0_wave); false when ESS is not strictly increasing over the points
+// order: mppi_search.hpp, essps_round0_wave); false when ESS is not strictly increasing over the points
 template <int NPT>
 MPPI_SEARCH_HD bool essps_poly(const double* lgrid, const double* ess, double target_ess, int j0, double& log_lam) {
     bool increasing = true;

@@ -1,5 +1,5 @@
 // mppi_common.hpp — Shared definitions of the gfx950 kernels: launch geometry (Dims), the noise identity (GenCtx), wave reductions.
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "host_search.hpp"

@@ -1,5 +1,5 @@
 // mppi_env.hpp — The control tick around the solver without the host: map lookups for callers outside the solver, calc_ref_trajectory, env.step (example/racing.py:161-266).
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include "mppi_common.hpp"
 

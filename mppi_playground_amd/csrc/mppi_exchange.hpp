@@ -1,5 +1,6 @@
 // mppi_exchange.hpp — The sharded solve's only exchange without a collective launch: peer-to-peer buffers over xGMI (tagged 8-byte cells).
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
+// (p2p_publish_kernel / p2p_collect_kernel are defined in capi_exchange.hip: summarize_kernel and finalize_kernel use the helpers.)
 #pragma once
 #include "mppi_common.hpp"
 
@@ -26,14 +27,6 @@ __device__ __forceinline__ void p2p_store(unsigned long long* p, unsigned long l
 }
 __device__ __forceinline__ unsigned long long p2p_load(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__global__ __launch_bounds__(BLOCK) void p2p_publish_kernel(const float* __restrict__ summary, int len, P2pCtx x) {
-    const size_t slot = ((size_t)(x.seq & 1u) * x.world + x.rank) * x.lenp;
-    for (int j = threadIdx.x; j < len; j += BLOCK) {
-        const unsigned long long cell = ((unsigned long long)x.seq << 32) | (unsigned long long)__float_as_uint(summary[j]);
-        for (int w = 0; w < x.world; ++w) p2p_store(x.peers[w] + slot + j, cell);
-    }
 }
 
 // Block-wide: wait for the `len` cells of every rank of solve x.seq and unpack them to out[w * stride + j].
@@ -64,11 +57,6 @@ __device__ __forceinline__ void p2p_collect(const P2pCtx& x, int len, float* __r
         out[w * stride + j] = __uint_as_float((unsigned)cell);
     }
     __syncthreads();
-}
-
-// self-test / generic use: collect into a plain device array [W][len]
-__global__ __launch_bounds__(BLOCK) void p2p_collect_kernel(P2pCtx x, int len, float* __restrict__ out) {
-    p2p_collect<BLOCK>(x, len, out, len);
 }
 
 }  // namespace mppi

@@ -1,5 +1,5 @@
 // mppi_finalize.hpp — Fold of the partial rows (summarize_kernel), combine of the shard summaries, normalise, Savitzky-Golay step, warm start, batch-1 rollout (mppi.py:381-452,508-524): finalize_kernel, state_seq_kernel.
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include "mppi_exchange.hpp"
 #include "mppi_reduce.hpp"
@@ -41,71 +41,9 @@ __device__ __forceinline__ int compact_live_rows(const float* __restrict__ heads
     return nlive;
 }
 
-// Sum the per-block partial rows into the shard summary {min c, sum e, sum e^2, sum e*c, A[row]}.  Only blocks
-// that saw a live tile published a row (heads[b][3]); every block of this kernel first compacts the ascending
-// list of those rows, then thread (c = tid & 15, g = tid >> 4) of block x sums list entries g, g+64, ... of
-// column 16x + c (64 B coalesced row segments, 8 loads in flight) and the 64 row groups combine through LDS.
-// The last block folds the three scalar heads.  Deterministic (fixed order).  With a sharp softmax the list
-// holds a handful of rows and the kernel is launch-latency only.
+// geometry of summarize_kernel (defined in capi_solve.hip, the one unit that launches it)
 constexpr int SUM_COLS = 16;
 constexpr int SUM_BLOCK = 1024;
-__global__ __launch_bounds__(SUM_BLOCK) void summarize_kernel(const float* __restrict__ partials,
-                                                          const float* __restrict__ heads,
-                                                          const unsigned* __restrict__ min_key, int nblocks,
-                                                          int colsp, int row, float* __restrict__ summary,
-                                                          float* __restrict__ summary_copy,
-                                                          int* __restrict__ nlive_out, P2pCtx p2p) {
-    constexpr int NG = SUM_BLOCK / SUM_COLS;
-    __shared__ float s_part[NG][SUM_COLS + 1];
-    __shared__ unsigned short s_list[REDUCE_MAX_BLOCKS];
-    __shared__ int s_wcnt[REDUCE_MAX_BLOCKS / WAVE];
-    const int nlive = compact_live_rows<SUM_BLOCK>(heads, nblocks, s_list, s_wcnt);
-    const int c = threadIdx.x & (SUM_COLS - 1), g = threadIdx.x / SUM_COLS;
-    const bool head_block = blockIdx.x == gridDim.x - 1;
-    float a[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) a[q] = 0.f;
-    const int col = blockIdx.x * SUM_COLS + c;
-    const bool active = head_block ? c < 3 : col < colsp;
-    const float* base = head_block ? heads + c : partials + col;
-    const int64_t ld = head_block ? 4 : colsp;
-    if (active) {
-        for (int k = g; k < nlive; k += 8 * NG) {  // 8 independent loads in flight per thread
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int kk = k + q * NG;
-                if (kk < nlive) a[q] += base[(int64_t)s_list[kk] * ld];
-            }
-        }
-    }
-    s_part[g][c] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-    __syncthreads();
-    if (threadIdx.x < SUM_COLS) {
-        float v = 0.f;
-        for (int q = 0; q < NG; ++q) v += s_part[q][threadIdx.x];
-        int dst = -1;
-        if (!head_block) {
-            const int cc = blockIdx.x * SUM_COLS + threadIdx.x;
-            if (cc < row) dst = MPPI_SUMMARY_HEAD + cc;
-        } else {
-            if (threadIdx.x < 3) dst = 1 + threadIdx.x;
-            if (threadIdx.x == 3) {
-                dst = 0;
-                v = key_to_float(*min_key);
-                if (nlive_out) *nlive_out = nlive;
-            }
-        }
-        if (dst >= 0) {
-            summary[dst] = v;
-            if (summary_copy) summary_copy[dst] = v;
-            if (p2p.seq) {  // cells are self-contained: every block hands its own columns to the peers right away
-                const size_t slot = ((size_t)(p2p.seq & 1u) * p2p.world + p2p.rank) * p2p.lenp + dst;
-                const unsigned long long cell = ((unsigned long long)p2p.seq << 32) | (unsigned long long)__float_as_uint(v);
-                for (int w = 0; w < p2p.world; ++w) p2p_store(p2p.peers[w] + slot, cell);
-            }
-        }
-    }
-}
 
 // One trajectory rolled out from explicit actions (reference layout row) or from noise, writing the
 // states the reference would leave in its state buffer.  GETU(t, u) fills the action of step t.

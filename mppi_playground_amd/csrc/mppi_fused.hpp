@@ -1,5 +1,5 @@
 // mppi_fused.hpp — MPPI.forward() as ONE cooperative launch for small problems: solve_fused_kernel.
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include "mppi_rollout.hpp"
 #include "mppi_finalize.hpp"

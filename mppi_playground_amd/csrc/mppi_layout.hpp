@@ -1,5 +1,5 @@
 // mppi_layout.hpp — Reference layout [N][T][dc] <-> lane-major noise tiles (inject / export), staged through LDS.
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include "mppi_common.hpp"
 

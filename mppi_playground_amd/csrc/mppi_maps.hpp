@@ -1,5 +1,5 @@
 // mppi_maps.hpp — Map construction on the device: obstacle rasteriser, lane corridor, padded copies (bit-exact with the reference's host loops).
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include "mppi_common.hpp"
 

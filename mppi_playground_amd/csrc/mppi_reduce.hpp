@@ -1,5 +1,5 @@
 // mppi_reduce.hpp — Steps 5-6 (mppi.py:376-384): softmax weights and the weighted sum of the clamped actions as per-block partial rows — weights_reduce_kernel.
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include "mppi_sample.hpp"
 

@@ -1,5 +1,5 @@
 // mppi_rollout.hpp — Steps 1b-3 (mppi.py:266-336): clamp, N x T rollout and stage / terminal costs — rollout_cost_kernel (lane per trajectory) and the literal wavefront-per-trajectory variant.
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include "mppi_sample.hpp"
 

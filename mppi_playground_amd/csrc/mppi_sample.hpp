@@ -1,5 +1,5 @@
 // mppi_sample.hpp — Step 1 (mppi.py:255-263): the device noise stream (gen_noise4 is its definition), sample_kernel, posterior draws.
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include "mppi_common.hpp"
 

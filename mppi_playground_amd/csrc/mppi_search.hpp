@@ -1,5 +1,6 @@
 // mppi_search.hpp — Step 4 on the device (mppi.py:341-370,387-398): softmax statistics for 1 / 32 temperatures, the ESSPS / LBPS searches and the MPO step as kernels.
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
+// (The kernels that are not templates are defined in capi_search.hip: mppi_fused.hpp includes this header too.)
 #pragma once
 #include "mppi_common.hpp"
 
@@ -41,23 +42,6 @@ __device__ __forceinline__ float stats_partial_fold(const float (*s_p)[4], int j
     for (int w = 1; w < BLOCK / WAVE; ++w) v = j == 3 ? fmaxf(v, s_p[w][3]) : v + s_p[w][j];
     return v;
 }
-__global__ __launch_bounds__(BLOCK) void stats_partial_kernel(const float* __restrict__ costs, int64_t N,
-                                                             const unsigned* __restrict__ min_key, float lambda_arg,
-                                                             const float* __restrict__ lambda_dev /* nullable */,
-                                                             float* __restrict__ part /*[STATS_BLOCKS][4]*/) {
-    __shared__ float s_p[BLOCK / WAVE][4];
-    const float lambda = lambda_dev ? *lambda_dev : lambda_arg;
-    const float cmin = key_to_float(*min_key);
-    const float xmax = (-cmin) / lambda;
-    float se, se2, sec, cmax;
-    stats_partial_thread([&](int64_t i, int) { return costs[i]; }, N, (int64_t)blockIdx.x * BLOCK + threadIdx.x,
-                         (int64_t)gridDim.x * BLOCK, lambda, xmax, se, se2, sec, cmax);
-    stats_partial_wave(se, se2, sec, cmax);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) { s_p[wid][0] = se; s_p[wid][1] = se2; s_p[wid][2] = sec; s_p[wid][3] = cmax; }
-    __syncthreads();
-    if (threadIdx.x < 4) part[blockIdx.x * 4 + threadIdx.x] = stats_partial_fold(s_p, threadIdx.x);
-}
 // One wave: the partial rows part[b][0..3], b < nblocks, summed in double in a fixed order (lane l takes rows l, l + 64, ...,
 // then a butterfly).  Every lane returns the totals.
 template <class Row>
@@ -70,16 +54,6 @@ __device__ __forceinline__ void stats_combine_wave(Row&& row, int nblocks, int l
     }
     se = wave_sum_bfly(se); se2 = wave_sum_bfly(se2); sec = wave_sum_bfly(sec);
     cmax = wave_max_bfly(cmax);
-}
-__global__ __launch_bounds__(WAVE) void stats_combine_kernel(const float* __restrict__ part, int nblocks,
-                                                            const unsigned* __restrict__ min_key,
-                                                            double* __restrict__ out /*[5] mapped host*/) {
-    double se, se2, sec;
-    float cmax;
-    stats_combine_wave([&](int b, int j) { return part[b * 4 + j]; }, nblocks, (int)threadIdx.x, se, se2, sec, cmax);
-    if (threadIdx.x == 0) {
-        out[0] = (double)key_to_float(*min_key); out[1] = (double)cmax; out[2] = se; out[3] = se2; out[4] = sec;
-    }
 }
 
 // The same statistics for up to STATS_L temperatures in one pass over the costs (a grid of lambdas
@@ -152,15 +126,6 @@ __device__ __forceinline__ float stats_multi_block(const float* __restrict__ cos
         for (int w = 0; w < NWV; ++w) v += (&s_p[w][0][0])[threadIdx.x];
     }
     return v;
-}
-__global__ __launch_bounds__(STATS_THREADS) void stats_multi_kernel(const float* __restrict__ costs, int64_t N,
-                                                                    const unsigned* __restrict__ min_key,
-                                                                    const float* __restrict__ lams,
-                                                                    float* __restrict__ part,
-                                                                    float* __restrict__ part_max /* nullable: [blocks] max c */) {
-    __shared__ StatsLds lds;
-    const float v = stats_multi_block(costs, N, key_to_float(*min_key), lams, part_max, lds);
-    if (threadIdx.x < STATS_L * 3) part[(int64_t)blockIdx.x * STATS_L * 3 + threadIdx.x] = v;
 }
 // Block-wide (960 of 1024 threads = 24 column quads x 40 row groups): column sums of part[nblocks][96] in double, fixed
 // order -> out[96] (LDS or global).  The partial rows were written by other XCDs a moment ago, so every load is a
@@ -244,11 +209,6 @@ __device__ __forceinline__ void stats_combine_columns(const Rows rows, int nbloc
 __device__ __forceinline__ void stats_combine_columns(const float* __restrict__ part, int nblocks, double* s_acc,
                                                       double* out) {
     stats_combine_columns(PartRows{part}, nblocks, s_acc, out);
-}
-__global__ __launch_bounds__(1024) void stats_multi_combine_kernel(const float* __restrict__ part, int nblocks,
-                                                                   double* __restrict__ out /*[STATS_L][3] mapped*/) {
-    __shared__ double s_acc[STATS_COMB_GROUPS * STATS_L * 3];
-    stats_combine_columns(part, nblocks, s_acc, out);
 }
 
 // ESSPS without leaving the device (mppi.py:351-370): after each 32-temperature statistics pass one block combines
@@ -359,19 +319,6 @@ __device__ __forceinline__ void essps_select_step(const double* s_sum, double* s
             lams[j] = (float)g;
         }
     }
-}
-__global__ __launch_bounds__(1024) void essps_select_kernel(const float* __restrict__ part, int nblocks, double target_ess,
-                                                            mppi::host::EsspsRange range, EsspsDev* __restrict__ st,
-                                                            float* __restrict__ lams, float* __restrict__ lams0,
-                                                            float* __restrict__ lambda_out,
-                                                            double* __restrict__ lambda_host) {
-    __shared__ double s_acc[STATS_COMB_GROUPS * STATS_L * 3];
-    __shared__ double s_sum[STATS_L * 3];
-    __shared__ double s_ess[STATS_L], s_grid[STATS_L], s_lgrid[STATS_L];
-    stats_combine_columns(part, nblocks, s_acc, s_sum);
-    if (threadIdx.x >= WAVE) return;  // the scalar step: one wave, lane j owns temperature j where that helps
-    essps_select_step<0>(s_sum, s_ess, s_grid, s_lgrid, target_ess, range, st, lams, lams0, lambda_out, lambda_host,
-                         (int)threadIdx.x);
 }
 // Round 1 — statistics over the refined grid AND its select step — as ONE launch that costs its launch floor when round 0
 // already finished the search (the warm-started first grid usually does: every block returns at once; as two kernels the
@@ -614,107 +561,6 @@ __device__ __forceinline__ bool brent_gather_wave(int nvb, const BrentCtx& bx, u
     if (probe == 1) cmax = wave_max_bfly(cmax);
     BRENT_TRACE(5);  // butterfly
     return !__any(timed_out);
-}
-__global__ __launch_bounds__(BRENT_THREADS) void lbps_brent_kernel(const float* __restrict__ costs, int64_t N,
-                                                                   const unsigned* __restrict__ min_key, int nvb, int per_thread,
-                                                                   double delta, double lam_min, double lam_max, BrentCtx bx,
-                                                                   float* __restrict__ lambda_out,
-                                                                   double* __restrict__ lambda_host /*[3]: next, used, probes*/) {
-    extern __shared__ float s_cost[];  // [per_thread][blockDim.x] when staged
-    __shared__ BrentLds L;
-    const int tid = threadIdx.x;
-    const bool staged = per_thread <= BRENT_STAGE_MAX;
-    const long long t0 = wall_clock64();
-    if (staged) {
-        const int vb = (int)blockIdx.x + BRENT_LANES * (tid >> 8);
-        int m = 0;
-        if (vb < nvb)
-            for (int64_t i = (int64_t)vb * BLOCK + (tid & (BLOCK - 1)); i < N; i += (int64_t)nvb * BLOCK, ++m)
-                s_cost[m * (int)blockDim.x + tid] = costs[i];  // (read back by the same thread only: no barrier needed)
-    }
-    if (tid == 0) {
-        L.go = 0;
-#ifdef MPPI_BRENT_TRACE
-        L.tlast = wall_clock64();
-        for (int k = 0; k < 8; ++k) L.trace[k] = 0;
-#endif
-    }
-    const float cmin = key_to_float(*min_key);
-    __syncthreads();
-    if (tid < WAVE) {  // wave 0: the search itself (every lane the same scalars); the probe's barriers pair with the loop below
-        unsigned probe = 0;
-        double lam = 0.0;
-        int nfev = 0;
-        float cmax_all = -INFINITY;  // (gathered with the first probe)
-        const bool ok = mppi::host::lbps_lambda(
-            [&](double x, mppi::host::SoftmaxStats& st) {
-                if (tid == 0) { L.lam = (float)x; L.xmax = (-cmin) / (float)x; L.go = 1; }
-                ++probe;
-                BRENT_TRACE(6);  // objective + Brent step
-                __syncthreads();  // (A) the other waves pick the temperature up
-                BRENT_TRACE(0);  // barrier A
-                brent_partials_block(costs, s_cost, staged, N, nvb, bx, probe, L);
-                BRENT_TRACE(3);  // barrier B
-                double se, se2, sec;
-                float cmax;
-                if (!brent_gather_wave(nvb, bx, probe, L, t0, se, se2, sec, cmax)) return false;
-                if (probe == 1) cmax_all = cmax;
-                st = mppi::host::SoftmaxStats{(double)cmin, (double)cmax_all, se, se2, sec};
-                return true;
-            },
-            delta, lam_min, lam_max, lam, &nfev);
-        if (tid == 0) L.go = 0;
-        __syncthreads();  // (A) releases the other waves for good
-        if (blockIdx.x == 0 && tid == 0) {
-            if (!ok) { lam = NAN; *bx.error = 1; }
-            *lambda_out = (float)lam;
-            lambda_host[0] = lam; lambda_host[1] = lam; lambda_host[2] = (double)nfev;
-#ifdef MPPI_BRENT_TRACE
-            BRENT_TRACE(7);
-            for (int k = 0; k < 8; ++k) bx.error[1 + k] = L.trace[k];
-#endif
-        }
-    } else {
-        unsigned probe = 0;
-        for (;;) {
-            __syncthreads();  // (A)
-            if (!L.go) break;
-            ++probe;
-            brent_partials_block(costs, s_cost, staged, N, nvb, bx, probe, L);
-        }
-    }
-}
-
-// MPO without leaving the device (mppi.py:191-200,387-398): the dual variable and its Adam moments live in device
-// memory; after the solve's weights one statistics pass at T = softplus(log T) (stats_partial_kernel reading T from
-// `temp_dev`) and this one-thread step (host_search.hpp: mpo_step — the arithmetic the CPU tests pin to the reference)
-// leave lambda = exp(log T) for the NEXT solve in `lambda_out`.
-__global__ __launch_bounds__(WAVE) void mpo_step_kernel(const float* __restrict__ part, int nblocks,
-                                                        const unsigned* __restrict__ min_key,
-                                                        mppi::host::MpoState* __restrict__ st,
-                                                        float* __restrict__ lambda_out, float* __restrict__ temp_dev,
-                                                        double* __restrict__ lambda_host /*[2]: next, used*/) {
-    double se = 0.0, se2 = 0.0, sec = 0.0;
-    float cmax = -INFINITY;
-    for (int b = threadIdx.x; b < nblocks; b += WAVE) {
-        se += part[b * 4]; se2 += part[b * 4 + 1]; sec += part[b * 4 + 2];
-        cmax = fmaxf(cmax, part[b * 4 + 3]);
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        se += __shfl_xor(se, m); se2 += __shfl_xor(se2, m); sec += __shfl_xor(sec, m);
-        cmax = fmaxf(cmax, __shfl_xor(cmax, m));
-    }
-    if (threadIdx.x == 0) {
-        mppi::host::MpoState s = *st;
-        const double used = (double)*lambda_out;
-        const mppi::host::SoftmaxStats ss{(double)key_to_float(*min_key), (double)cmax, se, se2, sec};
-        const double lam = mppi::host::mpo_step(s, ss);
-        *st = s;
-        *lambda_out = (float)lam;
-        *temp_dev = s.temperature();
-        lambda_host[0] = lam; lambda_host[1] = used;
-    }
 }
 
 }  // namespace mppi

@@ -1,5 +1,5 @@
 // mppi_topk.hpp — Queries after a solve: weights, re-rolls of given actions / samples, get_top_samples (mppi.py:462-487: radix select, sort, re-roll).
-// Part of the MPPI.forward() hot path for gfx950; see mppi_kernels.hpp for the map of the files.
+// Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include "mppi_rollout.hpp"
 #include "mppi_finalize.hpp"

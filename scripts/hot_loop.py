@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction census of the hot loop of rollout_cost_kernel<racing, fast, regen> from a hipcc -save-temps listing:
-    python scripts/hot_loop.py /tmp/v/<name>/mppi_capi-hip-amdgcn-amd-amdhsa-gfx950.s [--copy longest|unit_L|all] [--dump]
+    python scripts/hot_loop.py /tmp/v/<name>/capi_solve-hip-amdgcn-amd-amdhsa-gfx950.s [--copy longest|unit_L|all] [--dump]
 One iteration of a copy's loop = two racing steps + one float4 of noise.  The kernel holds one copy of the loop per
 launch-uniform variant (mppi_rollout.hpp: lane_cost): a start outside the position clamp, the reference's unit wheel base
 (ctx.unit_L, the copy the bench runs) and a general wheel base.  --copy longest (the default) is the longest

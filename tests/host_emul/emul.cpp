@@ -1,7 +1,7 @@
 // Host build of the product's model functors (mppi_playground_amd/csrc/mppi_models.hpp) for
 // pre-GPU debugging of the model math, both FAST variants.  TEST-ONLY: the product never loads this
 // library; it exists so that tests can compare the device functors' arithmetic with the oracle on
-// a machine without a GPU.  The trajectory walk mirrors trajectory_cost() in mppi_kernels.hpp but
+// a machine without a GPU.  The trajectory walk mirrors trajectory_cost() in mppi_rollout.hpp but
 // reads the reference layout eps[N][T][dc].
 #include <cmath>
 #include <cstdint>
@@ -12,7 +12,7 @@
 
 using namespace mppi;
 
-// The kernel's entry (trajectory_cost / lane_cost in mppi_kernels.hpp): models with EntryGeneral wrap any finite heading
+// The kernel's entry (trajectory_cost / lane_cost in mppi_rollout.hpp): models with EntryGeneral wrap any finite heading
 // once with the reference's operation and, when the start lies outside the position clamp, take the bounds-tested lookup
 // for the stage cost of step 0; the other models range-check the state (a bad lane is redone with the library math).
 template <int MODEL, bool FAST>

@@ -1,5 +1,5 @@
 // Host build of the product's temperature searches (mppi_playground_amd/csrc/host_search.hpp) for the CPU suite.
-// TEST-ONLY: the product calls the same header from mppi_capi.hip with statistics reduced on the device; here the
+// TEST-ONLY: the product calls the same header from capi_search.hip with statistics reduced on the device; here the
 // statistics callback is a plain double-precision loop over a cost array, so that the search logic (Brent's bounded
 // minimiser, the ESSPS grid + cubic, the MPO Adam step) can be compared with scipy / pi_mpc/_host.py without a GPU.
 #include <cmath>

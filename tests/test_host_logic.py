@@ -206,7 +206,7 @@ def test_fails_loudly_without_gpu():
 
 # ------------------------------------------------------------------ map recipes (what the device rasterises)
 def _recipe_raster(nx, ny, recipe):
-    """numpy statement of the integer rules of raster_obstacles_kernel / lane_map_kernel (mppi_kernels.hpp)."""
+    """numpy statement of the integer rules of raster_obstacles_kernel / lane_map_kernel (mppi_maps.hpp)."""
     ix, iy = np.meshgrid(np.arange(nx), np.arange(ny), indexing="ij")
     if recipe["kind"] == "lane":
         best = np.full((nx, ny), np.iinfo(np.int64).max)
