@@ -9,8 +9,8 @@ namespace mppi {
 __global__ __launch_bounds__(BLOCK) void p2p_publish_kernel(const float* __restrict__ summary, int len, P2pCtx x) {
     const size_t slot = ((size_t)(x.seq & 1u) * x.world + x.rank) * x.lenp;
     for (int j = threadIdx.x; j < len; j += BLOCK) {
-        const unsigned long long cell = ((unsigned long long)x.seq << 32) | (unsigned long long)__float_as_uint(summary[j]);
-        for (int w = 0; w < x.world; ++w) p2p_store(x.peers[w] + slot + j, cell);
+        const unsigned long long cell = cell_pack(x.seq, summary[j]);
+        for (int w = 0; w < x.world; ++w) cell_store<__HIP_MEMORY_SCOPE_SYSTEM>(x.peers[w] + slot + j, cell);
     }
 }
 
@@ -148,8 +148,7 @@ int mppi_p2p_exchange(mppi_handle_t h, const float* data_dev, float* gathered_ou
     if (!h || !data_dev || !gathered_out_dev) return fail(h, MPPI_E_INVALID, "bad p2p arguments");
     if (!h->xchg.p2p_connected) return fail(h, MPPI_E_STATE, "p2p: not connected");
     hipStream_t s = (hipStream_t)stream;
-    ++h->seq.p2p;
-    if (h->seq.p2p == 0) h->seq.p2p = 1;
+    next_tag(h->seq.p2p);
     const int len = MPPI_SUMMARY_HEAD + h->d.row;
     hipLaunchKernelGGL(p2p_publish_kernel, dim3(1), dim3(BLOCK), 0, s, data_dev, len, p2p_ctx(h));
     hipLaunchKernelGGL(p2p_collect_kernel, dim3(1), dim3(BLOCK), 0, s, p2p_ctx(h), len, gathered_out_dev);

@@ -153,7 +153,7 @@ int mppi_create(const MppiConfig* cfg, mppi_handle_t* out) {
     auto& se = h->search;
     HIP_TRY(h, se.stats_part.alloc((size_t)STATS_L * 3 * STATS_BLOCKS));
     HIP_TRY(h, se.round1_cells.alloc_set((size_t)STATS_L * 3 * STATS_BLOCKS, 0));
-    HIP_TRY(h, se.stats.alloc(8 + STATS_L * 3 + 3, true));
+    HIP_TRY(h, se.mirror.alloc(1, true));
     HIP_TRY(h, se.mpo_dev.alloc(1));
     HIP_TRY(h, se.mpo_temp_dev.alloc(1));
     HIP_TRY(h, se.lbps_dev.alloc(1));
@@ -260,7 +260,8 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
     ds.essps_lo = ss.essps_lo; ds.essps_hi = ss.essps_hi; ds.essps_range = ss.essps_range;
     ds.essps_prev_host = ss.essps_prev_host; ds.essps_prev_lo = ss.essps_prev_lo; ds.essps_prev_hi = ss.essps_prev_hi;
     ds.lambda_dev_valid = ss.lambda_dev_valid;
-    for (int i = 0; i < 3; ++i) ds.stats.host[8 + STATS_L * 3 + i] = ss.stats.host[8 + STATS_L * 3 + i];  // the temperature's host mirror
+    ds.mirror.host->lam_next = ss.mirror.host->lam_next; ds.mirror.host->lam_used = ss.mirror.host->lam_used;
+    ds.mirror.host->passes = ss.mirror.host->passes;
     auto &dr = dst->reduce, &sr = src->reduce;
     dr.last_reduce_blocks = 0;            // the partial rows of src's last reduction are not copied ...
     dr.summary_valid = sr.summary_valid || sr.last_reduce_blocks > 0;

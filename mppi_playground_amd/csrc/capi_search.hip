@@ -165,8 +165,20 @@ __global__ __launch_bounds__(WAVE) void mpo_step_kernel(const float* __restrict_
     }
 }
 
-static int stats_blocks(mppi_handle_t h) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(STATS_BLOCKS, (h->d.N + STATS_THREADS - 1) / STATS_THREADS));
+// Grid of a statistics pass: the 32-temperature one (STATS_THREADS) or the single-temperature one (BLOCK) — also the Brent
+// search's virtual blocks: its bit-equality with the host search rests on this being the number mppi_softmax_stats uses.
+static int stats_blocks(mppi_handle_t h, int threads = STATS_THREADS) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(STATS_BLOCKS, (h->d.N + threads - 1) / threads));
+}
+
+// One checker per rule (`ptrs`: the handle and the call's output pointers are there).
+static int check_essps(mppi_handle_t h, bool ptrs, double target_ess, double lam_min, double lam_max) {
+    const bool ok = ptrs && lam_min > 0.0 && lam_max > lam_min && target_ess > 0.0;  // (false for a NaN)
+    return ok ? MPPI_OK : fail(h, MPPI_E_INVALID, "bad essps arguments");
+}
+static int check_lbps(mppi_handle_t h, bool ptrs, double delta, double lam_min, double lam_max) {
+    const bool ok = ptrs && lam_min > 0.0 && lam_max > lam_min && delta > 0.0 && delta < 1.0;  // (false for a NaN)
+    return ok ? MPPI_OK : fail(h, MPPI_E_INVALID, "bad lbps arguments");
 }
 
 // The state of the device-resident ESSPS search for [lam_min, lam_max]: a cold (geometric) first grid; after that every
@@ -196,7 +208,7 @@ int mpo_upload(mppi_handle_t h, double lambda0, double epsilon, double lr, bool 
     HIP_TRY(h, hipMemcpy(h->search.mpo_temp_dev, &temp0, sizeof(float), hipMemcpyHostToDevice));
     if (!lambda_too) return MPPI_OK;  // (mppi_create: the dual exists, but no temperature has been asked for yet)
     HIP_TRY(h, hipMemcpy(h->search.lambda_dev, &lam0, sizeof(float), hipMemcpyHostToDevice));  // the first solve's temperature
-    h->search.stats.host[8 + STATS_L * 3] = h->search.stats.host[8 + STATS_L * 3 + 1] = lambda0;
+    h->search.mirror.host->lam_next = h->search.mirror.host->lam_used = lambda0;
     h->search.lambda_dev_valid = true;
     return MPPI_OK;
 }
@@ -209,16 +221,14 @@ int mppi_softmax_stats(mppi_handle_t h, float lambda, double* out5_host, void* s
     if (!h || !out5_host || !(lambda > 0.0f)) return fail(h, MPPI_E_INVALID, "bad softmax_stats arguments");
     hipStream_t s = (hipStream_t)stream;
     const unsigned* mk = h->core.min_key + h->seq.min_slot;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(STATS_BLOCKS, (h->d.N + BLOCK - 1) / BLOCK));
+    const int blocks = stats_blocks(h, BLOCK);
     hipLaunchKernelGGL(stats_partial_kernel, dim3(blocks), dim3(BLOCK), 0, s, h->core.costs, h->d.N, mk, lambda,
                        (const float*)nullptr, h->search.stats_part);
     HIP_TRY(h, hipGetLastError());
-    double* dev_out = nullptr;
-    dev_out = h->search.stats.dev;
-    hipLaunchKernelGGL(stats_combine_kernel, dim3(1), dim3(WAVE), 0, s, h->search.stats_part, blocks, mk, dev_out);
+    hipLaunchKernelGGL(stats_combine_kernel, dim3(1), dim3(WAVE), 0, s, h->search.stats_part, blocks, mk, &h->search.mirror.dev->single[0]);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(s));
-    for (int i = 0; i < 5; ++i) out5_host[i] = h->search.stats.host[i];
+    for (int i = 0; i < 5; ++i) out5_host[i] = h->search.mirror.host->single[i];
     return MPPI_OK;
 }
 
@@ -237,12 +247,10 @@ int mppi_softmax_stats_multi(mppi_handle_t h, const float* lambdas_host, int cou
     hipLaunchKernelGGL(stats_multi_kernel, dim3(blocks), dim3(STATS_THREADS), 0, s, h->core.costs, h->d.N, mk,
                        (const float*)h->search.lams_dev, h->search.stats_part, (float*)nullptr);
     HIP_TRY(h, hipGetLastError());
-    double* dev_out = nullptr;
-    dev_out = h->search.stats.dev;
-    hipLaunchKernelGGL(stats_multi_combine_kernel, dim3(1), dim3(1024), 0, s, h->search.stats_part, blocks, dev_out + 8);
+    hipLaunchKernelGGL(stats_multi_combine_kernel, dim3(1), dim3(1024), 0, s, h->search.stats_part, blocks, &h->search.mirror.dev->grid[0]);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(s));
-    for (int j = 0; j < count * 3; ++j) out_host[j] = h->search.stats.host[8 + j];
+    for (int j = 0; j < count * 3; ++j) out_host[j] = h->search.mirror.host->grid[j];
     return MPPI_OK;
 }
 
@@ -251,32 +259,25 @@ int mppi_softmax_stats_multi(mppi_handle_t h, const float* lambdas_host, int cou
 // temperature stays in HBM, where mppi_weights_reduce / mppi_finalize read it when called with MPPI_LAMBDA_DEVICE;
 // mppi_get_lambda fetches it (synchronises).  Same arithmetic as mppi_essps_lambda: both run host_search.hpp.
 int mppi_essps_lambda_device(mppi_handle_t h, double target_ess, double lam_min, double lam_max, void* stream) {
-    if (!h || !(lam_min > 0.0) || !(lam_max > lam_min) || !(target_ess > 0.0))
-        return fail(h, MPPI_E_INVALID, "bad essps arguments");
+    if (int rc = check_essps(h, h != nullptr, target_ess, lam_min, lam_max)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = essps_prepare(h, lam_min, lam_max)) return rc;
     const unsigned* mk = h->core.min_key + h->seq.min_slot;
     const int blocks = stats_blocks(h);
-    double* host_lam = nullptr;
-    host_lam = h->search.stats.dev;
-    host_lam += 8 + STATS_L * 3;
+    double* host_lam = &h->search.mirror.dev->lam_next;
     float* lams0 = h->search.lams_dev + STATS_L;
     float* lams1 = h->search.lams_dev + 2 * STATS_L;
     for (int r = 0; r < 2; ++r) {
-        if (++h->seq.round1 == 0u) h->seq.round1 = 1u;  // (the cells start out zeroed: 0 tags nothing)
-        if (r == 0 && h->opt.essps_merge0)
-            hipLaunchKernelGGL(essps_round_kernel<0>, dim3(blocks), dim3(STATS_THREADS), 0, s, h->core.costs, h->d.N, mk, target_ess,
-                               h->search.essps_range, h->search.essps_dev, lams1, lams0, h->search.lambda_dev, host_lam, h->search.round1_cells,
-                               h->seq.round1);
-        else if (r == 0) {
+        const unsigned tag = next_tag(h->seq.round1);
+        if (r == 0 && !h->opt.essps_merge0) {
             hipLaunchKernelGGL(stats_multi_kernel, dim3(blocks), dim3(STATS_THREADS), 0, s, h->core.costs, h->d.N, mk,
                                (const float*)lams0, h->search.stats_part, (float*)nullptr);
             hipLaunchKernelGGL(essps_select_kernel, dim3(1), dim3(1024), 0, s, (const float*)h->search.stats_part, blocks, target_ess,
                                h->search.essps_range, h->search.essps_dev, lams1, lams0, h->search.lambda_dev, host_lam);
         } else
-            hipLaunchKernelGGL(essps_round_kernel<1>, dim3(blocks), dim3(STATS_THREADS), 0, s, h->core.costs, h->d.N, mk, target_ess,
-                               h->search.essps_range, h->search.essps_dev, lams1, lams0, h->search.lambda_dev, host_lam, h->search.round1_cells,
-                               h->seq.round1);
+            hipLaunchKernelGGL(r == 0 ? essps_round_kernel<0> : essps_round_kernel<1>, dim3(blocks), dim3(STATS_THREADS), 0, s, h->core.costs,
+                               h->d.N, mk, target_ess, h->search.essps_range, h->search.essps_dev, lams1, lams0, h->search.lambda_dev, host_lam,
+                               h->search.round1_cells, tag);
     }
     HIP_TRY(h, hipGetLastError());
     h->search.lambda_dev_valid = true;
@@ -289,8 +290,8 @@ int mppi_get_lambda(mppi_handle_t h, double* lambda_out_host, double* lambda_use
     if (!h || !lambda_out_host) return fail(h, MPPI_E_INVALID, "null");
     if (!h->search.lambda_dev_valid) return fail(h, MPPI_E_STATE, "no temperature on the device");
     HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
-    *lambda_out_host = h->search.stats.host[8 + STATS_L * 3];
-    if (lambda_used_out_host) *lambda_used_out_host = h->search.stats.host[8 + STATS_L * 3 + 1];
+    *lambda_out_host = h->search.mirror.host->lam_next;
+    if (lambda_used_out_host) *lambda_used_out_host = h->search.mirror.host->lam_used;
     return MPPI_OK;
 }
 
@@ -299,50 +300,36 @@ int mppi_get_lambda(mppi_handle_t h, double* lambda_out_host, double* lambda_use
 int mppi_search_passes(mppi_handle_t h, void* stream) {
     if (!h || !h->search.lambda_dev_valid) return 0;
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return 0;
-    return (int)h->search.stats.host[8 + STATS_L * 3 + 2];
+    return (int)h->search.mirror.host->passes;
 }
 
 // LBPS with no host synchronisation (mppi.py:341-349): LBPS_ROUNDS x (32-temperature statistics pass -> one-block
 // grid step), the temperature stays in HBM (MPPI_LAMBDA_DEVICE).  See lbps_select_kernel.
 int mppi_lbps_lambda_device(mppi_handle_t h, double delta, double lam_min, double lam_max, void* stream) {
-    if (!h || !(lam_min > 0.0) || !(lam_max > lam_min) || !(delta > 0.0) || !(delta < 1.0))
-        return fail(h, MPPI_E_INVALID, "bad lbps arguments");
+    if (int rc = check_lbps(h, h != nullptr, delta, lam_min, lam_max)) return rc;
     hipStream_t s = (hipStream_t)stream;
     float* lams0 = h->search.lams_dev;              // (the caller's-grid slot doubles as LBPS's preset round-0 grid)
     float* lams1 = h->search.lams_dev + 2 * STATS_L;
-    if (h->search.lbps_lo != lam_min || h->search.lbps_hi != lam_max) {  // (re)build the round-0 grid: set-up path, blocking
-        LbpsDev st{};
-        float lamf[STATS_L];
-        mppi::host::essps_make_grid<STATS_L>(lam_min, lam_max, st.grid0);
-        for (int j = 0; j < STATS_L; ++j) { lamf[j] = (float)st.grid0[j]; st.grid[j] = st.grid0[j]; }
+    LbpsDev st{};
+    float lamf[STATS_L];
+    mppi::host::essps_make_grid<STATS_L>(lam_min, lam_max, st.grid0);
+    for (int j = 0; j < STATS_L; ++j) { lamf[j] = (float)st.grid0[j]; st.grid[j] = st.grid0[j]; }
+    if (h->search.lbps_lo != lam_min || h->search.lbps_hi != lam_max) {  // another range: the search state too (set-up path, blocking)
         HIP_TRY(h, hipDeviceSynchronize());
         HIP_TRY(h, hipMemcpy(h->search.lbps_dev, &st, sizeof(st), hipMemcpyHostToDevice));
         h->search.lbps_lo = lam_min; h->search.lbps_hi = lam_max;
     }
-    {   // the caller's-grid slot may have been overwritten by mppi_softmax_stats_multi: refresh it from the search state
-        float lamf[STATS_L];
-        double g0[STATS_L];
-        mppi::host::essps_make_grid<STATS_L>(lam_min, lam_max, g0);
-        for (int j = 0; j < STATS_L; ++j) lamf[j] = (float)g0[j];
-        if (int rc = upload_small(h, lams0, lamf, STATS_L, s)) return rc;
-    }
+    // the caller's-grid slot may have been overwritten by mppi_softmax_stats_multi: refresh it
+    if (int rc = upload_small(h, lams0, lamf, STATS_L, s)) return rc;
     const unsigned* mk = h->core.min_key + h->seq.min_slot;
     const int blocks = stats_blocks(h);
-    double* host_lam = nullptr;
-    host_lam = h->search.stats.dev;
-    host_lam += 8 + STATS_L * 3;
     for (int r = 0; r < LBPS_ROUNDS; ++r) {
         hipLaunchKernelGGL(stats_multi_kernel, dim3(blocks), dim3(STATS_THREADS), 0, s, h->core.costs, h->d.N, mk,
                            (const float*)(r == 0 ? lams0 : lams1), h->search.stats_part, h->search.stats_max);
-        if (r == 0)
-            hipLaunchKernelGGL((lbps_select_kernel<false, true>), dim3(1), dim3(1024), 0, s, (const float*)h->search.stats_part,
-                               (const float*)h->search.stats_max, blocks, mk, delta, h->search.lbps_dev, lams1, h->search.lambda_dev, host_lam);
-        else if (r < LBPS_ROUNDS - 1)
-            hipLaunchKernelGGL((lbps_select_kernel<false, false>), dim3(1), dim3(1024), 0, s, (const float*)h->search.stats_part,
-                               (const float*)h->search.stats_max, blocks, mk, delta, h->search.lbps_dev, lams1, h->search.lambda_dev, host_lam);
-        else
-            hipLaunchKernelGGL((lbps_select_kernel<true, false>), dim3(1), dim3(1024), 0, s, (const float*)h->search.stats_part,
-                               (const float*)h->search.stats_max, blocks, mk, delta, h->search.lbps_dev, lams1, h->search.lambda_dev, host_lam);
+        auto select = lbps_select_kernel<false, true>;  // <LAST, FIRST>: the rounds differ in nothing else
+        if (r > 0) select = r < LBPS_ROUNDS - 1 ? lbps_select_kernel<false, false> : lbps_select_kernel<true, false>;
+        hipLaunchKernelGGL(select, dim3(1), dim3(1024), 0, s, (const float*)h->search.stats_part, (const float*)h->search.stats_max, blocks,
+                           mk, delta, h->search.lbps_dev, lams1, h->search.lambda_dev, &h->search.mirror.dev->lam_next);
     }
     HIP_TRY(h, hipGetLastError());
     h->search.lambda_dev_valid = true;
@@ -357,8 +344,7 @@ int mppi_lbps_lambda_device(mppi_handle_t h, double delta, double lam_min, doubl
 // interpreter work per probe.
 int mppi_essps_lambda(mppi_handle_t h, double target_ess, double lam_min, double lam_max, double* lambda_out,
                       void* stream) {
-    if (!h || !lambda_out || !(lam_min > 0.0) || !(lam_max > lam_min) || !(target_ess > 0.0))
-        return fail(h, MPPI_E_INVALID, "bad essps arguments");
+    if (int rc = check_essps(h, h && lambda_out, target_ess, lam_min, lam_max)) return rc;
     constexpr int P = STATS_L;
     int rc = MPPI_OK;
     if (h->search.essps_prev_lo != lam_min || h->search.essps_prev_hi != lam_max) h->search.essps_prev_host.warm = false;  // another range: a cold search
@@ -383,12 +369,11 @@ int mppi_essps_lambda(mppi_handle_t h, double target_ess, double lam_min, double
 // mppi_softmax_stats bit for bit, gathered by every block through tagged cells — and leaves the temperature in HBM
 // (MPPI_LAMBDA_DEVICE) and in mapped host memory.  The same temperature as mppi_lbps_lambda, to the bit.
 int mppi_lbps_brent_device(mppi_handle_t h, double delta, double lam_min, double lam_max, void* stream) {
-    if (!h || !(lam_min > 0.0) || !(lam_max > lam_min) || !(delta > 0.0) || !(delta < 1.0))
-        return fail(h, MPPI_E_INVALID, "bad lbps arguments");
+    if (int rc = check_lbps(h, h != nullptr, delta, lam_min, lam_max)) return rc;
     hipStream_t s = (hipStream_t)stream;
     // the geometry of mppi_softmax_stats (stats_partial_kernel): nvb blocks of 256 threads, grid-stride over the costs;
     // block l of this launch runs the virtual blocks l, l + 64, ... (lane l's rows of stats_combine_kernel)
-    const int nvb = (int)std::max<int64_t>(1, std::min<int64_t>(STATS_BLOCKS, (h->d.N + BLOCK - 1) / BLOCK));
+    const int nvb = stats_blocks(h, BLOCK);
     const int64_t per_thread64 = (h->d.N + (int64_t)nvb * BLOCK - 1) / ((int64_t)nvb * BLOCK);
     const int grid = std::min(nvb, BRENT_LANES);
     const int threads = BLOCK * ((nvb + BRENT_LANES - 1) / BRENT_LANES);
@@ -410,12 +395,11 @@ int mppi_lbps_brent_device(mppi_handle_t h, double delta, double lam_min, double
     }
     const BrentCtx bx{h->search.brent_cells, h->search.error.dev, h->seq.brent, h->opt.fused_timeout_ticks};
     h->seq.brent += BRENT_SEQ_STRIDE;
-    double* host_lam = h->search.stats.dev + 8 + STATS_L * 3;
     // (test hook: with the last block missing, its lane's sums never arrive — what a block that is not resident looks like to
     // the others: every poll runs into the budget, the flag is raised and the temperature is NaN)
     hipLaunchKernelGGL(lbps_brent_kernel, dim3(grid - (h->search.brent_drop_block && grid > 1 ? 1 : 0)), dim3(threads), shmem, s, (const float*)h->core.costs, h->d.N,
                        (const unsigned*)(h->core.min_key + h->seq.min_slot), nvb, per_thread, delta, lam_min, lam_max, bx, h->search.lambda_dev,
-                       host_lam);
+                       &h->search.mirror.dev->lam_next);
     HIP_TRY(h, hipGetLastError());
     h->search.lambda_dev_valid = true;
     return MPPI_OK;
@@ -438,8 +422,7 @@ extern "C" int mppi_debug_brent_trace(mppi_handle_t h, int* out8) {  // 10 ns ti
 // lower-bound objective over [lam_min, lam_max]; every probe is one mppi_softmax_stats round trip (two tiny launches
 // + a 40-byte read-back through mapped host memory), with no interpreter in the loop.  Unsharded handles; synchronises.
 int mppi_lbps_lambda(mppi_handle_t h, double delta, double lam_min, double lam_max, double* lambda_out, void* stream) {
-    if (!h || !lambda_out || !(lam_min > 0.0) || !(lam_max > lam_min) || !(delta > 0.0) || !(delta < 1.0))
-        return fail(h, MPPI_E_INVALID, "bad lbps arguments");
+    if (int rc = check_lbps(h, h && lambda_out, delta, lam_min, lam_max)) return rc;
     int rc = MPPI_OK;
     const bool ok = mppi::host::lbps_lambda(
         [&](double lam, mppi::host::SoftmaxStats& st) {
@@ -466,14 +449,11 @@ int mppi_mpo_step_device(mppi_handle_t h, void* stream) {
     if (!h) return MPPI_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const unsigned* mk = h->core.min_key + h->seq.min_slot;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(STATS_BLOCKS, (h->d.N + BLOCK - 1) / BLOCK));
-    double* host_lam = nullptr;
-    host_lam = h->search.stats.dev;
-    host_lam += 8 + STATS_L * 3;
+    const int blocks = stats_blocks(h, BLOCK);
     hipLaunchKernelGGL(stats_partial_kernel, dim3(blocks), dim3(BLOCK), 0, s, h->core.costs, h->d.N, mk, 1.0f,
                        (const float*)h->search.mpo_temp_dev, h->search.stats_part);
     hipLaunchKernelGGL(mpo_step_kernel, dim3(1), dim3(WAVE), 0, s, (const float*)h->search.stats_part, blocks, mk, h->search.mpo_dev,
-                       h->search.lambda_dev, h->search.mpo_temp_dev, host_lam);
+                       h->search.lambda_dev, h->search.mpo_temp_dev, &h->search.mirror.dev->lam_next);
     HIP_TRY(h, hipGetLastError());
     h->search.lambda_dev_valid = true;
     return MPPI_OK;
@@ -508,7 +488,7 @@ int mppi_mpo_set_state(mppi_handle_t h, const double* in4_host) {
     HIP_TRY(h, hipMemcpy(h->search.mpo_dev, &st, sizeof(st), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->search.mpo_temp_dev, &temp, sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->search.lambda_dev, &lam, sizeof(float), hipMemcpyHostToDevice));
-    h->search.stats.host[8 + STATS_L * 3] = h->search.stats.host[8 + STATS_L * 3 + 1] = (double)lam;
+    h->search.mirror.host->lam_next = h->search.mirror.host->lam_used = (double)lam;
     h->search.lambda_dev_valid = true;
     return MPPI_OK;
 }

@@ -63,8 +63,8 @@ __global__ __launch_bounds__(SUM_BLOCK) void summarize_kernel(const float* __res
             if (summary_copy) summary_copy[dst] = v;
             if (p2p.seq) {  // cells are self-contained: every block hands its own columns to the peers right away
                 const size_t slot = ((size_t)(p2p.seq & 1u) * p2p.world + p2p.rank) * p2p.lenp + dst;
-                const unsigned long long cell = ((unsigned long long)p2p.seq << 32) | (unsigned long long)__float_as_uint(v);
-                for (int w = 0; w < p2p.world; ++w) p2p_store(p2p.peers[w] + slot, cell);
+                const unsigned long long cell = cell_pack(p2p.seq, v);
+                for (int w = 0; w < p2p.world; ++w) cell_store<__HIP_MEMORY_SCOPE_SYSTEM>(p2p.peers[w] + slot, cell);
             }
         }
     }
@@ -191,18 +191,14 @@ static int solve_fused(mppi_handle_t h, float lambda, float* action_out, float* 
     }
     if (!dev && !(lambda > 0.0f)) return fail(h, MPPI_E_INVALID, "lambda must be > 0");
     h->seq.min_slot ^= 1;
-    ++h->seq.fused;
-    if (h->seq.fused == 0) h->seq.fused = 1;
-    double* host_lam = nullptr;
-    host_lam = h->search.stats.dev;
-    host_lam += 8 + STATS_L * 3;
+    next_tag(h->seq.fused);
     FusedArgs A{};
     A.mean = h->core.mean; A.x0 = h->core.x0_cur; A.costs = h->core.costs;
     A.min_key = h->core.min_key + h->seq.min_slot; A.next_min_key = h->core.min_key + (h->seq.min_slot ^ 1);
     A.mean_used = h->core.mean_used; A.x0_used = h->core.x0_used;
     A.rule = rule; A.rule_param = h->search.auto_param; A.lam_min = h->search.auto_lo; A.lam_max = h->search.auto_hi;
     A.lambda_arg = dev ? -1.0f : lambda;
-    A.lambda_dev = h->search.lambda_dev; A.lambda_host = host_lam;
+    A.lambda_dev = h->search.lambda_dev; A.lambda_host = &h->search.mirror.dev->lam_next;
     A.grid0 = rule == FUSED_RULE_ESSPS ? h->search.essps_dev.p->grid0 : h->fused.grid0;
     A.lams0 = h->search.lams_dev + STATS_L;
     A.essps = h->search.essps_dev; A.range = h->search.essps_range;
@@ -413,8 +409,7 @@ int mppi_weights_reduce(mppi_handle_t h, float lambda, float* summary_out_dev, v
     h->reduce.summary_valid = false;
     P2pCtx p2p{};
     if (h->xchg.p2p_enabled) {  // summarize_kernel also hands the summary to every peer (and to this rank's own slot)
-        ++h->seq.p2p;
-        if (h->seq.p2p == 0) h->seq.p2p = 1;
+        next_tag(h->seq.p2p);
         p2p = p2p_ctx(h);
     }
     const bool many_rows = h->opt.fold_mode == 0 ? *(volatile int*)h->reduce.live_hint.host > FOLD_IN_FINALIZE_MAX_ROWS : h->opt.fold_mode == 2;

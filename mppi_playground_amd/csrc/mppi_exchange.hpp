@@ -2,6 +2,7 @@
 // Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 // (p2p_publish_kernel / p2p_collect_kernel are defined in capi_exchange.hip: summarize_kernel and finalize_kernel use the helpers.)
 #pragma once
+#include "mppi_cells.hpp"
 #include "mppi_common.hpp"
 
 namespace mppi {
@@ -9,8 +10,7 @@ namespace mppi {
 // ------------------------------------------------------------------------------------------
 // One-shot peer-to-peer exchange of the shard summaries (the sharded solve's only exchange) without a collective
 // launch: every rank stores its summary straight into all peers' exchange buffers over xGMI and the consumer
-// polls its own buffer.  Cells are 8 bytes {fp32 value, 32-bit sequence number} written with ONE store, so data and
-// "ready" flag cannot be seen apart (the idea of RCCL's low-latency protocol): no fence ordering is relied on.
+// polls its own buffer.  Tagged cells (mppi_cells.hpp) of system scope: {fp32 value, the solve's sequence number}.
 // Buffer of rank r (fine-grained device memory, IPC-mapped into every peer): cells[2][W][lenp]; solve `seq` uses
 // parity seq & 1 — a rank can be at most one solve ahead of the slowest one, because its next finalize needs
 // everybody's summary of that solve.
@@ -22,13 +22,6 @@ struct P2pCtx {
     unsigned seq;                      // 0 = exchange off
 };
 
-__device__ __forceinline__ void p2p_store(unsigned long long* p, unsigned long long v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ unsigned long long p2p_load(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // Block-wide: wait for the `len` cells of every rank of solve x.seq and unpack them to out[w * stride + j].
 // Polls give up after ~20 s of wall clock (100 MHz counter) and raise *x.error; the caller's results are then void.
 template <int NT>
@@ -38,9 +31,9 @@ __device__ __forceinline__ void p2p_collect(const P2pCtx& x, int len, float* __r
     for (int idx = threadIdx.x; idx < x.world * len; idx += NT) {
         const int w = idx / len, j = idx - w * len;
         const unsigned long long* cellp = x.local + ((size_t)(x.seq & 1u) * x.world + w) * x.lenp + j;
-        unsigned long long cell = p2p_load(cellp);
+        unsigned long long cell = cell_load<__HIP_MEMORY_SCOPE_SYSTEM>(cellp);
         unsigned spins = 0;
-        while ((unsigned)(cell >> 32) != x.seq) {
+        while (cell_tag(cell) != x.seq) {
             if ((++spins & 255u) == 0u && wall_clock64() - t0 > 2000000000ll) {
                 *x.error = 1;
                 if (s_timed_out) *s_timed_out = 1;  // (LDS) the block voids this solve's outputs
@@ -52,9 +45,9 @@ __device__ __forceinline__ void p2p_collect(const P2pCtx& x, int len, float* __r
             if (spins < 64u) __builtin_amdgcn_s_sleep(2);
             else if (spins < 1024u) __builtin_amdgcn_s_sleep(32);
             else __builtin_amdgcn_s_sleep(127);
-            cell = p2p_load(cellp);
+            cell = cell_load<__HIP_MEMORY_SCOPE_SYSTEM>(cellp);
         }
-        out[w * stride + j] = __uint_as_float((unsigned)cell);
+        out[w * stride + j] = cell_f32(cell);
     }
     __syncthreads();
 }

@@ -16,10 +16,8 @@ namespace mppi {
 // threads (at most 32 blocks up to 4096 trajectories), block b owning `spb` consecutive trajectories (one per thread of
 // its first spb/64 waves — ONE wave as long as CUs are left: small problems spread over many CUs as lone waves, exactly
 // like the stand-alone rollout kernel; the other waves of a block share its reductions and the regeneration of its
-// weighted noise rows) — and the blocks talk through CELLS in HBM instead of kernel boundaries: an 8-byte word
-// {fp32 value, 32-bit solve number} written with ONE relaxed agent-scope store and polled with agent-scope loads, so that
-// data and "ready" cannot be seen apart and no fence or grid barrier is needed (the protocol of the peer-to-peer
-// exchange, P2pCtx; a device-scope fence per block costs far more than a kernel boundary on this part).  A round trip
+// weighted noise rows) — and the blocks talk through tagged CELLS in HBM instead of kernel boundaries ({fp32 value, this
+// solve's number}: mppi_cells.hpp — no fence, no grid barrier).  A round trip
 // through a cell costs about as much as a kernel boundary (~2.5 us), so the exchanges are arranged in as few DEPENDENT
 // round trips as possible and every reader issues all its loads before it looks at the first one (fx_get_many):
 //   more than 32 blocks:
@@ -62,22 +60,21 @@ __device__ __forceinline__ unsigned long long* fx_cell(const FusedCtx& x, int ph
     return x.cells + ((size_t)phase * FUSED_MAX_BLOCKS + b) * FX_CELLS + j;
 }
 __device__ __forceinline__ void fx_put(const FusedCtx& x, int phase, int b, int j, float v) {
-    __hip_atomic_store(fx_cell(x, phase, b, j), ((unsigned long long)x.seq << 32) | (unsigned long long)__float_as_uint(v),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    cell_store(fx_cell(x, phase, b, j), cell_pack(x.seq, v));
 }
 __device__ __forceinline__ float fx_wait(const FusedCtx& x, const unsigned long long* p, unsigned long long cell, long long t0,
                                          bool& timed_out) {
     unsigned spins = 0;
-    while ((unsigned)(cell >> 32) != x.seq) {
+    while (cell_tag(cell) != x.seq) {
         if ((++spins & 255u) == 0u && wall_clock64() - t0 > x.timeout_ticks) { timed_out = true; break; }
         __builtin_amdgcn_s_sleep(2);
-        cell = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        cell = cell_load(p);
     }
-    return __uint_as_float((unsigned)cell);
+    return cell_f32(cell);
 }
 __device__ __forceinline__ float fx_get(const FusedCtx& x, int phase, int b, int j, long long t0, bool& timed_out) {
     const unsigned long long* p = fx_cell(x, phase, b, j);
-    return fx_wait(x, p, __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), t0, timed_out);
+    return fx_wait(x, p, cell_load(p), t0, timed_out);
 }
 // cell j of blocks b0, b0 + bstep, ... (n <= K of them): ALL loads are issued before the first tag is looked at, so the
 // K cells cost one round trip, not K
@@ -87,7 +84,7 @@ __device__ __forceinline__ void fx_get_many(const FusedCtx& x, int phase, int b0
     unsigned long long c[K];
 #pragma unroll
     for (int k = 0; k < K; ++k)
-        if (k < n) c[k] = __hip_atomic_load(fx_cell(x, phase, b0 + k * bstep, j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k < n) c[k] = cell_load(fx_cell(x, phase, b0 + k * bstep, j));
 #pragma unroll
     for (int k = 0; k < K; ++k) out[k] = k < n ? fx_wait(x, fx_cell(x, phase, b0 + k * bstep, j), c[k], t0, timed_out) : 0.0f;
 }

@@ -16,6 +16,7 @@
 //   capi_exchange.hip  RCCL loader, comm / p2p exchanges, time-out flags             (+ the p2p kernels)
 // Kernel headers, one per stage.  A kernel that is not a template is defined in the one unit that launches it.
 //   mppi_common.hpp    Dims, GenCtx, wave reductions
+//   mppi_cells.hpp     the tagged 8-byte cell: how blocks of one launch and peer devices hand values over (search, fused, exchange)
 //   mppi_sample.hpp    step 1: the noise stream (gen_noise4), sample_kernel, posterior draws
 //   mppi_rollout.hpp   steps 1b-3: rollout_cost_kernel (THE hot loop: trajectory_cost), the wavefront-per-trajectory variant
 //   mppi_reduce.hpp    steps 5-6: weights_reduce_kernel
@@ -31,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types and prototypes only: the library is dlopen()ed when a communicator is asked for
 
+#include <cstddef>
 #include <cstring>
 #include <string>
 #include <utility>
@@ -94,6 +96,15 @@ struct ErrorFlag : Pinned<int> {
     int get() const { return host ? *(volatile int*)host : 0; }  // (read without synchronising)
     void clear() { if (host) *(volatile int*)host = 0; }
 };
+
+// What the statistics and search kernels write to mapped host memory (each is handed the device address of the field it fills).
+struct SearchMirror {
+    double single[8];          // one temperature: {min c, max c, sum e, sum e^2, sum e*c} (stats_combine_kernel)
+    double grid[STATS_L * 3];  // 32 temperatures: {sum e, sum e^2, sum e*c} each (stats_multi_combine_kernel)
+    double lam_next, lam_used, passes;  // a device-resident rule's temperature for the next solve, the last weights' one, its passes / probes
+};
+static_assert(offsetof(SearchMirror, grid) == 8 * sizeof(double), "device writes land where they did");
+static_assert(offsetof(SearchMirror, lam_next) == (8 + STATS_L * 3) * sizeof(double), "device writes land where they did");
 
 struct Event {
     hipEvent_t e = nullptr;
@@ -177,7 +188,7 @@ struct MppiSolver {
         DevBuf<float> stats_part;      // [STATS_BLOCKS][max(4, STATS_L*3)]
         DevBuf<float> stats_max;       // [STATS_BLOCKS] per-block maximum cost (LBPS: the cost range)
         DevBuf<float> lams_dev;        // [3][STATS_L]: caller's grid, ESSPS round-0 grid (preset), ESSPS round-1 grid (device-written)
-        Pinned<double> stats;          // mapped [8 + STATS_L*3 + 3]: single-lambda stats, grid stats, device-searched lambda (next, used), its passes
+        Pinned<SearchMirror> mirror;   // mapped, one element
         DevBuf<float> lambda_dev;      // the temperature that search left on the device (MPPI_LAMBDA_DEVICE)
         bool lambda_dev_valid = false;
         // the rule mppi_solve applies when called with MPPI_LAMBDA_DEVICE (mppi_set_auto_lambda)
@@ -386,6 +397,8 @@ inline int check_ready(mppi_handle_t h) {
     return MPPI_OK;
 }
 
+// the tag of the next use of a cell buffer (mppi_cells.hpp): 0 is skipped, it tags nothing
+inline unsigned next_tag(unsigned& seq) { if (++seq == 0u) seq = 1u; return seq; }
 inline P2pCtx p2p_ctx(mppi_handle_t h) {
     const auto& x = h->xchg;
     return P2pCtx{x.p2p_peers_dev, x.p2p_local, x.p2p_error.dev, x.p2p_world, x.p2p_rank, x.p2p_lenp, h->seq.p2p};

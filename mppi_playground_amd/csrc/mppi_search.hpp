@@ -2,6 +2,7 @@
 // Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 // (The kernels that are not templates are defined in capi_search.hip: mppi_fused.hpp includes this header too.)
 #pragma once
+#include "mppi_cells.hpp"
 #include "mppi_common.hpp"
 
 namespace mppi {
@@ -143,8 +144,8 @@ struct PartRows {
     }
     __device__ __forceinline__ float4 finish(int, int, const Raw& r) const { return r.v; }
 };
-// ... or 8-byte {value, launch number} cells the blocks of THIS launch are still writing (relaxed agent-scope stores: data
-// and readiness in one store, no fence — the hand-off of the single-launch solve): polled until the tag is this launch's.
+// ... or tagged cells {value, launch number} (mppi_cells.hpp) the blocks of THIS launch are still writing: polled until
+// the tag is this launch's.
 struct CellRows {
     const unsigned long long* cells;  // [blocks][96]
     unsigned seq;
@@ -155,7 +156,7 @@ struct CellRows {
     }
     __device__ __forceinline__ void issue(int bb, int quad, Raw& r) const {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) r.c[c] = __hip_atomic_load(at(bb, quad) + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int c = 0; c < 4; ++c) r.c[c] = cell_load(at(bb, quad) + c);
     }
     __device__ __forceinline__ float4 finish(int bb, int quad, const Raw& r) const {
         float o[4];
@@ -163,11 +164,11 @@ struct CellRows {
         for (int c = 0; c < 4; ++c) {
             unsigned long long cell = r.c[c];
             // (no time-out: the writers wait for nothing, every one of them gets its turn on the device)
-            while ((unsigned)(cell >> 32) != seq) {
+            while (cell_tag(cell) != seq) {
                 __builtin_amdgcn_s_sleep(2);
-                cell = __hip_atomic_load(at(bb, quad) + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                cell = cell_load(at(bb, quad) + c);
             }
-            o[c] = __uint_as_float((unsigned)cell);
+            o[c] = cell_f32(cell);
         }
         return make_float4(o[0], o[1], o[2], o[3]);
     }
@@ -345,9 +346,7 @@ __global__ __launch_bounds__(STATS_THREADS) void essps_round_kernel(const float*
     // after the last read of this round's temperatures)
     const float v = stats_multi_block(costs, N, key_to_float(*min_key), ROUND == 0 ? lams0 : lams, nullptr, u.stats);
     if (threadIdx.x < STATS_L * 3)
-        __hip_atomic_store(cells + (int64_t)blockIdx.x * STATS_L * 3 + threadIdx.x,
-                           ((unsigned long long)seq << 32) | (unsigned long long)__float_as_uint(v), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+        cell_store(cells + (int64_t)blockIdx.x * STATS_L * 3 + threadIdx.x, cell_pack(seq, v));
     if (blockIdx.x != 0) return;
     __syncthreads();  // u.stats is dead from here on
     stats_combine_columns(CellRows{cells, seq}, (int)gridDim.x, u.acc, s_sum);
@@ -422,8 +421,7 @@ __global__ __launch_bounds__(1024) void lbps_select_kernel(const float* __restri
 // launch of G = min(64, nvb) blocks, nvb = the blocks of stats_partial_kernel's grid ("virtual blocks": 256 threads, the
 // same threads own the same costs and add them in the same order), the costs staged once in LDS.  Block l runs the virtual
 // blocks l, l + 64, l + 128, l + 192 — exactly the partial rows LANE l of stats_combine_kernel adds up — so per probe it
-// publishes that lane's three double sums as six 8-byte {half, probe tag} cells (one relaxed agent-scope store each: data
-// and readiness cannot be seen apart, no fence — the protocol of essps_round_kernel / solve_fused_kernel); wave 0 of EVERY
+// publishes that lane's three double sums as six tagged cells {half, probe tag} (mppi_cells.hpp); wave 0 of EVERY
 // block then gathers the G lanes' sums (lane l polls block l's cells: one wave per CU on the memory system, one round of
 // latency), finishes the sum with stats_combine_kernel's butterfly and takes the SAME Brent step in double precision:
 // identical inputs, identical code, so all blocks agree on the next temperature and nothing is broadcast — one dependent
@@ -467,7 +465,28 @@ struct BrentLds {
 #ifndef BRENT_POLL_SLEEP
 #define BRENT_POLL_SLEEP 1
 #endif
-__device__ __forceinline__ void brent_publish_wave(int nvb, const BrentCtx& bx, unsigned probe, const BrentLds& L, int lane);
+// Wave 1 after (B): this block's lane sums (stats_combine_wave's loop over its rows: blockIdx.x, + 64, ... ascending, like
+// lane blockIdx.x of the combine) and its maximum, published as seven tagged cells.
+__device__ __forceinline__ void brent_publish_wave(int nvb, const BrentCtx& bx, unsigned probe, const BrentLds& L, int lane) {
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    float mx = -INFINITY;
+    for (int g = 0; g < BRENT_GROUPS; ++g)
+        if ((int)blockIdx.x + BRENT_LANES * g < nvb) {
+            const float (*wp)[4] = L.p + g * (BLOCK / WAVE);
+            a0 += stats_partial_fold(wp, 0); a1 += stats_partial_fold(wp, 1); a2 += stats_partial_fold(wp, 2);
+            mx = fmaxf(mx, stats_partial_fold(wp, 3));
+        }
+    const unsigned tag = bx.seq0 + probe;
+    unsigned long long* mine = bx.cells + ((size_t)(probe & 1u) * BRENT_LANES + blockIdx.x) * BRENT_CELLS;
+    if (lane < (probe == 1 ? 7 : 6)) {
+        const unsigned long long b0 = (unsigned long long)__double_as_longlong(a0), b1 = (unsigned long long)__double_as_longlong(a1),
+                                 b2 = (unsigned long long)__double_as_longlong(a2);
+        const unsigned half = lane == 0 ? (unsigned)b0 : lane == 1 ? (unsigned)(b0 >> 32) : lane == 2 ? (unsigned)b1
+                            : lane == 3 ? (unsigned)(b1 >> 32) : lane == 4 ? (unsigned)b2 : lane == 5 ? (unsigned)(b2 >> 32)
+                            : __float_as_uint(mx);
+        cell_store(mine + lane, cell_pack(tag, half));
+    }
+}
 // The block's share of one probe, by every thread: the partial sums of its virtual blocks, per wave, into L.p (ends with
 // the barrier that publishes them to wave 0).
 __device__ __forceinline__ void brent_partials_block(const float* __restrict__ costs, const float* s_cost, bool staged, int64_t N,
@@ -501,29 +520,6 @@ __device__ __forceinline__ void brent_partials_block(const float* __restrict__ c
     // memory for a write-through store — before it can look at a load issued after it: one counter, in order)
     if (wid == 1) brent_publish_wave(nvb, bx, probe, L, lane);
 }
-// Wave 1 after (B): this block's lane sums (stats_combine_wave's loop over its rows: blockIdx.x, + 64, ... ascending, like
-// lane blockIdx.x of the combine) and its maximum, published as seven tagged cells.
-__device__ __forceinline__ void brent_publish_wave(int nvb, const BrentCtx& bx, unsigned probe, const BrentLds& L, int lane) {
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    float mx = -INFINITY;
-    for (int g = 0; g < BRENT_GROUPS; ++g)
-        if ((int)blockIdx.x + BRENT_LANES * g < nvb) {
-            const float (*wp)[4] = L.p + g * (BLOCK / WAVE);
-            a0 += stats_partial_fold(wp, 0); a1 += stats_partial_fold(wp, 1); a2 += stats_partial_fold(wp, 2);
-            mx = fmaxf(mx, stats_partial_fold(wp, 3));
-        }
-    const unsigned tag = bx.seq0 + probe;
-    unsigned long long* mine = bx.cells + ((size_t)(probe & 1u) * BRENT_LANES + blockIdx.x) * BRENT_CELLS;
-    if (lane < (probe == 1 ? 7 : 6)) {
-        const unsigned long long b0 = (unsigned long long)__double_as_longlong(a0), b1 = (unsigned long long)__double_as_longlong(a1),
-                                 b2 = (unsigned long long)__double_as_longlong(a2);
-        const unsigned half = lane == 0 ? (unsigned)b0 : lane == 1 ? (unsigned)(b0 >> 32) : lane == 2 ? (unsigned)b1
-                            : lane == 3 ? (unsigned)(b1 >> 32) : lane == 4 ? (unsigned)b2 : lane == 5 ? (unsigned)(b2 >> 32)
-                            : __float_as_uint(mx);
-        __hip_atomic_store(mine + lane, ((unsigned long long)tag << 32) | (unsigned long long)half, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
 // Wave 0 after (B): every lane's sums gathered (lane l polls block l's cells), then the butterfly.  Every lane returns the
 // totals; false = a poll timed out.
 __device__ __forceinline__ bool brent_gather_wave(int nvb, const BrentCtx& bx, unsigned probe, BrentLds& L, long long t0,
@@ -538,23 +534,21 @@ __device__ __forceinline__ bool brent_gather_wave(int nvb, const BrentCtx& bx, u
         const int ncell = probe == 1 ? 7 : 6;  // (the maximum travels with the first probe only)
         unsigned long long c[7];
 #pragma unroll
-        for (int j = 0; j < 7; ++j) c[j] = j < ncell ? __hip_atomic_load(theirs + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+        for (int j = 0; j < 7; ++j) c[j] = j < ncell ? cell_load(theirs + j) : 0ull;
         for (unsigned spins = 1;; ++spins) {
             bool all = true;
 #pragma unroll
-            for (int j = 0; j < 7; ++j) all = all && (j >= ncell || (unsigned)(c[j] >> 32) == tag);
+            for (int j = 0; j < 7; ++j) all = all && (j >= ncell || cell_tag(c[j]) == tag);
             if (all) break;
             // (the clock is a trip to the memory clock domain: looked at once in 64 rounds, not in every one)
             if ((spins & 63u) == 0u && wall_clock64() - t0 > bx.timeout_ticks) { timed_out = true; break; }
             __builtin_amdgcn_s_sleep(BRENT_POLL_SLEEP);
 #pragma unroll
             for (int j = 0; j < 7; ++j)
-                if (j < ncell) c[j] = __hip_atomic_load(theirs + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (j < ncell) { const unsigned long long v = cell_load(theirs + j); c[j] = v; }  // (a local: the listing of the measured loop)
         }
-        se = __longlong_as_double((long long)((c[1] << 32) | (c[0] & 0xFFFFFFFFull)));
-        se2 = __longlong_as_double((long long)((c[3] << 32) | (c[2] & 0xFFFFFFFFull)));
-        sec = __longlong_as_double((long long)((c[5] << 32) | (c[4] & 0xFFFFFFFFull)));
-        if (probe == 1) cmax = __uint_as_float((unsigned)c[6]);
+        se = cell_f64(c[0], c[1]); se2 = cell_f64(c[2], c[3]); sec = cell_f64(c[4], c[5]);
+        if (probe == 1) cmax = cell_f32(c[6]);
     }
     BRENT_TRACE(4);  // gather
     se = wave_sum_bfly(se); se2 = wave_sum_bfly(se2); sec = wave_sum_bfly(sec);
