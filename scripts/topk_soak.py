@@ -2,7 +2,8 @@
 """Randomised soak of the one-launch get_top_samples (mppi_top_samples, N <= 4096, k <= 1024): synthetic cost vectors of
 awkward shapes handed to the library (mppi_set_costs), the k winners against a host sort of the same costs —
 weights in order, and (costs without ties) the re-rolled trajectories bit-equal to the index-driven re-roll of the
-host's order.  Usage (GPU box): python scripts/topk_soak.py [cases]"""
+host's order.  --multi-launch: the same for the multi-launch path (histogram passes, collect, LDS or HBM sort, re-roll):
+N in 4097..200000, any k in 1..N.  Usage (GPU box): python scripts/topk_soak.py [--multi-launch] [cases]"""
 import os
 import sys
 
@@ -15,7 +16,9 @@ import mppi_playground_amd  # noqa: F401
 from envs import classic_control as cc
 from pi_mpc.mppi import MPPI
 
-cases = int(sys.argv[1]) if len(sys.argv) > 1 else 3000
+multi = "--multi-launch" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a != "--multi-launch"]
+cases = int(args[0]) if args else 3000
 rng = np.random.default_rng(20260927)
 
 
@@ -47,15 +50,19 @@ def draw(N):
 
 
 solvers = {}
-bad = 0
+bad = rerolled = 0
 by_kind = [0] * 10
 for case in range(cases):
-    N = int(rng.choice([rng.integers(1, 4097), rng.integers(1000, 4097), 1024, 1025, 2048, 4096, 4000]))
-    k = int(min(N, rng.choice([rng.integers(1, 1025), 1, 64, 300, 1000, 1024, N])))
-    k = min(k, 1024)
+    if multi:  # (sizes around the 2048-sample blocks of the select; k around the LDS sort's 1024 and the HBM sort's 2^m)
+        N = int(rng.choice([rng.integers(4097, 200001), rng.integers(4097, 200001), rng.integers(4097, 20001), 2048 * int(rng.integers(3, 98)) + 1]))
+        k = int(min(N, rng.choice([rng.integers(1, N + 1), rng.integers(1, N + 1), rng.integers(1, 4098), 1, 1024, 1025, 2049, N])))
+    else:
+        N = int(rng.choice([rng.integers(1, 4097), rng.integers(1000, 4097), 1024, 1025, 2048, 4096, 4000]))
+        k = int(min(N, rng.choice([rng.integers(1, 1025), 1, 64, 300, 1000, 1024, N])))
+        k = min(k, 1024)
     key = N
     if key not in solvers:
-        if len(solvers) > 24:
+        if len(solvers) > (4 if multi else 24):
             solvers.clear()
             torch.cuda.empty_cache()
         s = MPPI(horizon=10, num_samples=N, dim_state=2, dim_control=1, dynamics=cc.pendulum_dynamics, cost_func=cc.pendulum_cost,
@@ -81,8 +88,10 @@ for case in range(cases):
     ref /= ref.sum()
     got = w.cpu().numpy()
     ok = got.shape == (k,) and np.all(np.isfinite(got)) and np.abs(got - ref[order]).max() <= 2e-5 * ref.max()
+    ok = ok and (not multi or bool(np.all(np.diff(got) <= 0)))
     tie_free = len(np.unique(costs[order])) == k and (k == N or costs[order][-1] < np.partition(costs, k)[k])
     if ok and tie_free:
+        rerolled += 1
         out2 = torch.empty_like(out)
         idx = torch.from_numpy(order.astype(np.int64)).cuda()
         s._h.call("mppi_rollout_samples", idx.data_ptr(), k, out2.data_ptr(), st)
@@ -90,5 +99,8 @@ for case in range(cases):
     if not ok:
         bad += 1
         print(f"MISMATCH case {case}: N={N} k={k} kind={kind} tie_free={tie_free}", flush=True)
-print(f"{cases} cases (N in 1..4096, k in 1..1024; per kind of cost vector: {by_kind}): {bad} mismatches")
+if multi:
+    print(f"{cases} cases (multi-launch: N in 4097..200000, k in 1..N; per kind of cost vector: {by_kind}; {rerolled} re-rolls compared): {bad} mismatches")
+else:
+    print(f"{cases} cases (N in 1..4096, k in 1..1024; per kind of cost vector: {by_kind}): {bad} mismatches")
 sys.exit(1 if bad else 0)

@@ -2194,8 +2194,10 @@ def test_extreme_initial_states_against_oracle(model):
 
 
 def test_top_samples_with_tied_costs():
-    """Radix select when many costs are bit-identical: all equal, two plateaus with the k-th rank inside a plateau,
-    and negative / zero costs (key order across the sign)."""
+    """Many bit-identical costs: all equal, two plateaus with the k-th rank inside a plateau, and negative / zero costs (key
+    order across the sign).  At N = 4096 and k <= 1000 mppi_top_samples takes the one-launch path (the select inside
+    topk_rollout_kernel); the multi-launch radix select sees the same three vectors at N = 5000 in
+    test_top_candidates_are_exactly_the_k_smallest (tied_cost_vectors)."""
     solver, _ = make_solver("pendulum", 10, 4096, lambda_=1.0)
     x0 = torch.tensor([1.0, 0.0])
     solver.forward(x0)
@@ -2967,6 +2969,33 @@ def test_single_launch_solve_at_edge_sizes_against_oracle(model, T, N, expl):
         mean = a.cpu().numpy()  # the warm start of the next solve
 
 
+def topk_cost_vector(rng, N, kind):
+    """The ten kinds of awkward cost vectors of the top-k tests (and of scripts/topk_soak.py)."""
+    if kind == 0:
+        c = rng.uniform(77e3, 110e3, N)
+    elif kind == 1:
+        c = np.exp(rng.uniform(-20, 20, N))
+    elif kind == 2:
+        c = 5.0 + rng.integers(0, 40, N) * np.float32(4.8e-7)
+    elif kind == 3:
+        c = rng.integers(0, max(2, N // 50), N).astype(np.float64)
+    elif kind == 4:
+        c = rng.standard_normal(N) * 10.0 ** rng.integers(-3, 6)
+    elif kind == 5:
+        c = np.full(N, float(rng.uniform(-5, 5)))
+    elif kind == 6:
+        c = rng.uniform(0, 100, N)
+        c[rng.random(N) < 0.2] = np.inf
+    elif kind == 7:
+        c = np.sort(rng.uniform(0, 1e4, N))[:: (1 if rng.random() < 0.5 else -1)]
+    elif kind == 8:
+        c = rng.uniform(0, 1, N)
+        c[rng.integers(0, N, max(1, N // 8))] = c[rng.integers(0, N)]
+    else:  # a running racing loop: collision penalties of 10^4 per step on top of a few thousand
+        c = rng.uniform(300, 3000, N) + 1e4 * rng.integers(0, 25, N) * (rng.random(N) < 0.4)
+    return np.ascontiguousarray(c, dtype=np.float32)
+
+
 def test_one_launch_top_k_on_randomised_cost_vectors():
     """The one-launch get_top_samples (N <= 4096, k <= 1024: value-binned select, compaction, two-level rank sort, re-roll) on
     cost vectors of awkward shapes — one exponent, a range of e^40, 40 distinct values a few ulps apart, plateaus, mixed signs,
@@ -2975,32 +3004,6 @@ def test_one_launch_top_k_on_randomised_cost_vectors():
     scripts/topk_soak.py, whose 4 000 cases are recorded in profiles/r05_topk_soak.txt.)"""
     _need_gpu()
     rng = np.random.default_rng(7)
-
-    def draw(N, kind):
-        if kind == 0:
-            c = rng.uniform(77e3, 110e3, N)
-        elif kind == 1:
-            c = np.exp(rng.uniform(-20, 20, N))
-        elif kind == 2:
-            c = 5.0 + rng.integers(0, 40, N) * np.float32(4.8e-7)
-        elif kind == 3:
-            c = rng.integers(0, max(2, N // 50), N).astype(np.float64)
-        elif kind == 4:
-            c = rng.standard_normal(N) * 10.0 ** rng.integers(-3, 6)
-        elif kind == 5:
-            c = np.full(N, float(rng.uniform(-5, 5)))
-        elif kind == 6:
-            c = rng.uniform(0, 100, N)
-            c[rng.random(N) < 0.2] = np.inf
-        elif kind == 7:
-            c = np.sort(rng.uniform(0, 1e4, N))[:: (1 if rng.random() < 0.5 else -1)]
-        elif kind == 8:
-            c = rng.uniform(0, 1, N)
-            c[rng.integers(0, N, max(1, N // 8))] = c[rng.integers(0, N)]
-        else:  # a running racing loop: collision penalties of 10^4 per step on top of a few thousand
-            c = rng.uniform(300, 3000, N) + 1e4 * rng.integers(0, 25, N) * (rng.random(N) < 0.4)
-        return np.ascontiguousarray(c, dtype=np.float32)
-
     x0 = torch.tensor([1.0, 0.0])
     for N in (4000, 1024, 1025, 4096, 2731, 77):
         solver, _ = make_solver("pendulum", 10, N, lambda_=1.0)
@@ -3008,7 +3011,7 @@ def test_one_launch_top_k_on_randomised_cost_vectors():
         st = solver._stream()
         for kind in range(10):
             for k in sorted({1, min(N, 64), min(N, 300), min(N, 1024), int(rng.integers(1, min(N, 1024) + 1))}):
-                costs = draw(N, kind)
+                costs = topk_cost_vector(rng, N, kind)
                 fin = costs[np.isfinite(costs)]
                 lam = float(max(1e-3, np.ptp(fin))) if fin.size else 1.0
                 c = torch.from_numpy(costs).cuda()
@@ -3029,6 +3032,303 @@ def test_one_launch_top_k_on_randomised_cost_vectors():
                     idx = torch.from_numpy(order.astype(np.int64)).cuda()
                     solver._h.call("mppi_rollout_samples", idx.data_ptr(), k, out2.data_ptr(), st)
                     assert torch.equal(out, out2), (N, kind, k)
+
+
+# ------------------------------------------------------------------------------ the multi-launch get_top_samples
+# (N, the k's): every shape takes topk_hist_kernel<0/1/2> + topk_collect_kernel, then the LDS sort (k <= 1024) or the bitonic
+# sort in HBM over P = 2^m >= k words (k > 1024: topk_pad_kernel, topk_sort_local_kernel, topk_sort_global_kernel)
+MULTI_LAUNCH_SHAPES = (
+    # a select grid of 2 blocks; k > 1024 forces this path at N <= 4096: P = 2048 with 1023 pads, P = 2048 with none, P = 4096
+    (3000, (1025, 2048, 3000)),
+    # the first N beyond the one-launch path: k = 1, the largest k of the LDS sort, k = N (P = 8192)
+    (4097, (1, 1024, 4097)),
+    # the LDS sort of a partly filled row, one word past it, 2049 = 2047 pads, k = N: P = 8192 = three merge sizes
+    (5000, (300, 1025, 2049, 5000)),
+    # 35 blocks with a ragged last one; P up to 65536
+    (70001, (64, 1024, 4096, 40000)),
+    # beyond 1024 blocks x 2048 samples: the select grid is capped, every block takes a second, ragged stride
+    (2 * 1024 * 1024 + 4097, (300, 2049)),
+)
+MULTI_LAUNCH_SEED = 4  # (picked among 0 .. 30 so that at least half of the cases below are free of ties: see the floor)
+
+
+def multi_launch_cases():
+    """(N, kind, costs, ks) of test_multi_launch_top_k_on_randomised_cost_vectors: one vector per (N, kind), numpy alone.
+    The largest N runs three kinds only (one exponent, plateaus, mixed signs)."""
+    rng = np.random.default_rng(MULTI_LAUNCH_SEED)
+    for N, ks in MULTI_LAUNCH_SHAPES:
+        for kind in (range(10) if N < (1 << 21) else (0, 3, 4)):
+            yield N, kind, topk_cost_vector(rng, N, kind), ks
+
+
+def tie_free(costs, order, k):
+    """The host's order of the k smallest costs is the only one: no two of them equal, none equal to the (k+1)-th."""
+    return len(np.unique(costs[order])) == k and (k == len(costs) or costs[order][-1] < np.partition(costs, k)[k])
+
+
+def count_tie_free_multi_launch_cases():
+    """(cases, tie-free cases) of multi_launch_cases() — the floor literal of the test below; needs no GPU."""
+    cases = free = 0
+    for N, _, costs, ks in multi_launch_cases():
+        full = np.lexsort((np.arange(N), costs))
+        for k in ks:
+            cases, free = cases + 1, free + bool(tie_free(costs, full[:k], k))
+    return cases, free
+
+
+def _host_softmax(costs, lam):
+    x = (-costs) / np.float32(lam)  # (fp32 quotients like the device's)
+    ref = np.exp((x - x.max()).astype(np.float64))
+    return ref / ref.sum()
+
+
+def _temperature_for(costs):
+    fin = costs[np.isfinite(costs)]
+    return float(max(1e-3, np.ptp(fin))) if fin.size else 1.0
+
+
+def _top_samples_of(solver, c_dev, k, lam):
+    """mppi_set_costs -> mppi_weights_reduce -> mppi_finalize -> mppi_top_samples on a pendulum T = 10 handle."""
+    st = solver._stream()
+    solver._h.call("mppi_set_costs", c_dev.data_ptr(), 1, st)
+    solver._h.call("mppi_weights_reduce", lam, None, st)
+    a = torch.empty(10, 1, device="cuda")
+    solver._h.call("mppi_finalize", None, 1, lam, 0, a.data_ptr(), None, None, st)
+    out, w = torch.empty(k, 11, 2, device="cuda"), torch.empty(k, device="cuda")
+    solver._h.call("mppi_top_samples", k, lam, out.data_ptr(), w.data_ptr(), st)
+    return out, w
+
+
+def test_multi_launch_top_k_on_randomised_cost_vectors():
+    """The multi-launch get_top_samples (everything beyond N <= 4096 with k <= 1024: three histogram passes, collect, pad,
+    LDS or HBM sort, re-roll — the path of the full-size configurations and of both sharded halves) on the ten kinds of
+    awkward cost vectors of the one-launch test, at shapes on its edges (MULTI_LAUNCH_SHAPES), against a host sort of the
+    same costs: the weights finite, non-increasing and within 2e-5 of the largest (the one-launch test's limit) of the host's
+    softmax in (cost, index) order; without ties the trajectories bit-equal to the index-driven re-roll of the host's
+    order; the first state row = x0.  Every (N, k) runs twice in a row on the same handle: the second call sees the select
+    state (hist, counters) the first one left.
+    The re-roll comparison must be reached by at least 78 of the 146 cases: that is what numpy alone gives for the committed
+    seed (count_tie_free_multi_launch_cases(), no GPU) and more than half of them."""
+    _need_gpu()
+    x0 = torch.tensor([1.0, 0.0])
+    solver, cases, rerolled = None, 0, 0
+    for N, kind, costs, ks in multi_launch_cases():
+        if solver is None or solver._num_samples != N:
+            solver, _ = make_solver("pendulum", 10, N, lambda_=1.0)
+            solver.forward(x0)
+            st = solver._stream()
+        lam = _temperature_for(costs)
+        full = np.lexsort((np.arange(N), costs))  # ascending cost, then index
+        ref = _host_softmax(costs, lam)
+        c = torch.from_numpy(costs).cuda()
+        for k in ks:
+            assert N > 4096 or k > 1024  # (the multi-launch path)
+            order = full[:k]
+            free = tie_free(costs, order, k)
+            cases, rerolled = cases + 1, rerolled + bool(free)
+            if free:
+                want = torch.empty(k, 11, 2, device="cuda")
+                idx = torch.from_numpy(order.astype(np.int64)).cuda()
+                solver._h.call("mppi_rollout_samples", idx.data_ptr(), k, want.data_ptr(), st)
+            for rep in range(2):
+                out, w = _top_samples_of(solver, c, k, lam)
+                got = w.cpu().numpy()
+                err = np.abs(got - ref[order]).max()
+                print(f"multi-launch top-k N={N} kind={kind} k={k} rep={rep}: weights off by {err / ref.max():.2e} of the largest, tie_free={free}")
+                assert np.all(np.isfinite(got)) and np.all(np.diff(got) <= 0), (N, kind, k, rep)
+                assert err <= 2e-5 * ref.max(), (N, kind, k, rep)
+                if free:
+                    assert torch.equal(out, want), (N, kind, k, rep)
+                assert torch.equal(out[:, 0, :], x0.cuda().expand(k, 2)), (N, kind, k, rep)
+    assert cases == 146 and rerolled >= 78, (cases, rerolled)
+
+
+def _float_to_key(c):
+    """csrc/mppi_common.hpp float_to_key: negative floats -> ~bits, the others -> bits | 0x80000000 (unsigned order = float order,
+    -0.0 before +0.0)."""
+    b = np.ascontiguousarray(c, dtype=np.float32).view(np.uint32)
+    return np.where((b & np.uint32(0x80000000)) != 0, ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def _key_to_float(key):
+    """csrc/mppi_common.hpp key_to_float, the inverse."""
+    key = np.ascontiguousarray(key, dtype=np.uint32)
+    return np.where((key & np.uint32(0x80000000)) != 0, key & np.uint32(0x7FFFFFFF), ~key).astype(np.uint32).view(np.float32)
+
+
+def tied_cost_vectors(N):
+    """The three vectors of test_top_samples_with_tied_costs at N samples: all equal; two plateaus (the lower one holds every
+    third sample, so any k > ceil(N / 3) ends inside the upper one, which spans every block); -3.0, +0.0, -0.0 and positives."""
+    return {"all equal": np.full(N, 5.0, np.float32),
+            "two plateaus": np.where(np.arange(N) % 3 == 0, 1.0, 2.0).astype(np.float32),
+            "signs and zeros": np.concatenate([np.full(100, -3.0), np.zeros(100), -np.zeros(100),
+                                               np.linspace(0.5, 9, N - 300)]).astype(np.float32)}
+
+
+def _top_candidates_of(handle, c_dev, k, st):
+    """mppi_set_costs -> mppi_top_candidates: the k words as uint64 on the host."""
+    handle.call("mppi_set_costs", c_dev.data_ptr(), 1, st)
+    words = torch.empty(k, dtype=torch.int64, device="cuda")
+    handle.call("mppi_top_candidates", k, words.data_ptr(), st)
+    return words.cpu().numpy().view(np.uint64)
+
+
+def _check_candidates(words, costs, host_keys, sorted_keys, k, offset, tag):
+    key = (words >> np.uint64(32)).astype(np.uint32)
+    index = (words & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    assert words.shape == (k,) and len(np.unique(index)) == k, tag
+    assert index.min() >= offset and index.max() < offset + len(costs), tag
+    assert np.array_equal(host_keys[index - offset], key), tag
+    assert np.array_equal(_key_to_float(key).view(np.uint32), costs[index - offset].view(np.uint32)), tag
+    assert np.array_equal(np.sort(key), sorted_keys[:k]), tag  # exactly the k smallest keys, as a multiset
+    below = np.flatnonzero(host_keys < sorted_keys[k - 1]) + offset
+    assert np.isin(below, index).all(), tag  # nobody strictly below the k-th key is left out
+
+
+def _pendulum_shard(T, n_local, offset, n_global, x0_dev):
+    """A pendulum solver whose handle is re-created as the shard [offset, offset + n_local) of n_global samples (the recipe of
+    test_shard_invariance_and_combine), rolled out once around a zero mean with the noise of solve index 1."""
+    from mppi_playground_amd import _capi
+
+    sol, _ = make_solver("pendulum", T, n_local, lambda_=1.0)
+    cfg = _capi.MppiConfig()
+    cfg.model, cfg.horizon, cfg.dim_state, cfg.dim_control = _capi.MODEL_IDS["pendulum"], T, 2, 1
+    cfg.num_samples, cfg.sample_offset, cfg.inherit_count = n_local, offset, n_global
+    cfg.u_min[0], cfg.u_max[0], cfg.sigmas[0] = (MODEL_CFG["pendulum"][q][0] for q in ("u_min", "u_max", "sigmas"))
+    cfg.seed, cfg.device = 42, 0
+    sol._h.close()
+    sol._h = _capi.Handle(cfg)
+    sol._uploaded, sol._params_set, sol._ref_uploaded = {}, None, None
+    sol._h.call("mppi_set_state", C.c_void_p(x0_dev.data_ptr()), 1, sol._stream())
+    sol._refresh_model_inputs()
+    sol._h.call("mppi_sample", 1, sol._stream())
+    sol._h.call("mppi_rollout_cost", sol._stream())
+    return sol
+
+
+def test_top_candidates_are_exactly_the_k_smallest():
+    """mppi_top_candidates (the multi-launch radix select at every N and k; the first half of the sharded get_top_samples) returns
+    EXACTLY the k smallest costs — a statement that holds under ties, where the re-roll comparison has nothing to say: the
+    words decode (key = word >> 32, index = word & 0xffffffff) to distinct indices of this shard whose costs have those keys,
+    the multiset of keys is that of the host's k smallest, and every sample strictly below the k-th key is present.  On the
+    ten kinds of topk_cost_vector and the three tied vectors of test_top_samples_with_tied_costs (the k-th rank inside a
+    plateau that spans every block, one 11-bit / 22-bit prefix for all keys, -0.0 before +0.0, +inf inside the top k), with k
+    on both sides of 1024; on a handle with a sample_offset beyond 2^31 (the indices are GLOBAL); and interleaved with
+    mppi_top_samples, which cleans the select state by other means (its rollout kernel, not a memset)."""
+    _need_gpu()
+    probe = np.array([-np.inf, -3.0, -1e-40, -0.0, 0.0, 1e-40, 5.0, np.inf], np.float32)
+    assert np.all(np.diff(_float_to_key(probe).astype(np.int64)) > 0)
+    assert np.array_equal(_key_to_float(_float_to_key(probe)).view(np.uint32), probe.view(np.uint32))
+    rng = np.random.default_rng(11)
+    x0 = torch.tensor([1.0, 0.0])
+
+    def run(handle, st, N, offset, kinds):
+        vectors = {f"kind {kind}": topk_cost_vector(rng, N, kind) for kind in kinds} | tied_cost_vectors(N)
+        for name, costs in vectors.items():
+            c = torch.from_numpy(costs).cuda()
+            host_keys = _float_to_key(costs)
+            sorted_keys = np.sort(host_keys)
+            for k in (250, 300, 1000, 1024, 1025, N // 2, (9 * N) // 10, N):
+                words = _top_candidates_of(handle, c, k, st)
+                _check_candidates(words, costs, host_keys, sorted_keys, k, offset, (N, offset, name, k))
+                index = (words & np.uint64(0xFFFFFFFF)).astype(np.int64) - offset
+                if name == "two plateaus" and k > (N + 2) // 3:  # every sample of the lower plateau, the rest from the upper one
+                    assert np.count_nonzero(costs[index] == 1.0) == (N + 2) // 3, (N, k)
+                if name == "signs and zeros" and k == 250:  # the -3.0's, ALL the -0.0's (samples 200 .. 299), 50 of the +0.0's
+                    assert np.isin(np.arange(200, 300), index).all() and np.count_nonzero((index >= 100) & (index < 200)) == 50
+                if name == "kind 6" and k == N:  # reaches into the infinite costs
+                    assert np.count_nonzero(np.isinf(costs[index])) == np.count_nonzero(np.isinf(costs)) > 0
+
+    solver = None
+    for N in (3000, 4097, 5000, 70001):
+        solver, _ = make_solver("pendulum", 10, N, lambda_=1.0)
+        run(solver._h, solver._stream(), N, 0, range(10))
+    # global sample indices: a shard whose samples lie beyond 2^31
+    offset = 3_000_000_000
+    shard = _pendulum_shard(10, 4097, offset, offset + 4097, x0.cuda())
+    run(shard._h, shard._stream(), 4097, offset, (1, 3))
+    # mppi_top_candidates / mppi_top_samples / mppi_top_candidates on one handle (N = 70001): the third call sees the state the
+    # rollout kernel cleaned, and returns what the first one did
+    solver.forward(x0)
+    st = solver._stream()
+    for name, costs in (("kind 1", topk_cost_vector(rng, 70001, 1)), ("two plateaus", tied_cost_vectors(70001)["two plateaus"])):
+        c = torch.from_numpy(costs).cuda()
+        host_keys = _float_to_key(costs)
+        sorted_keys = np.sort(host_keys)
+        for k in (300, 1025, 40000):
+            first = _top_candidates_of(solver._h, c, k, st)
+            out, w = _top_samples_of(solver, c, k, _temperature_for(costs))
+            assert torch.isfinite(w).all() and torch.equal(out[:, 0, :], x0.cuda().expand(k, 2))
+            third = _top_candidates_of(solver._h, c, k, st)
+            for words in (first, third):
+                _check_candidates(words, costs, host_keys, sorted_keys, k, 0, (name, k))
+            assert np.array_equal(np.sort(first >> np.uint64(32)), np.sort(third >> np.uint64(32))), (name, k)
+            if name == "kind 1" and k <= 1025:
+                assert tie_free(costs, np.lexsort((np.arange(70001), costs))[:k], k)  # (numpy alone: the seed above)
+                assert np.array_equal(np.sort(first), np.sort(third)), (name, k)
+
+
+def test_rollout_candidates_merge_equals_the_unsharded_query():
+    """The sharded get_top_samples without the transport: one synthetic cost vector of 70001 samples split over three shard
+    handles of uneven sizes (30000 / 25000 / 15001) on this device, mppi_top_candidates(k) from each, the 3k words merged on
+    the host the way pi_mpc/_queries.py does (sort, keep the k smallest), and mppi_rollout_candidates on shard 0 — k = 300
+    straight from the caller's buffer, k = 1025 through the in-place large-k sort of a copy — against mppi_top_samples on one
+    unsharded handle with the same costs, seed and solve index: the weights to 2e-5 of the largest (the shards' summaries are
+    combined by mppi_finalize(num_shards = 3)), the trajectories bit-equal where the order is free of ties.  Regenerated noise
+    throughout: a handle with injected noise must refuse foreign candidates with MPPI_E_STATE."""
+    _need_gpu()
+    from mppi_playground_amd import _capi
+
+    N, T, sizes = 70001, 10, (30000, 25000, 15001)
+    x0 = torch.tensor([1.0, 0.0])
+    x0_dev = x0.cuda()
+    full, _ = make_solver("pendulum", T, N, lambda_=1.0)
+    full.forward(x0)  # solve index 1, zero mean: what _pendulum_shard rolls out
+    offsets = np.concatenate([[0], np.cumsum(sizes)])
+    assert offsets[-1] == N
+    shards = [_pendulum_shard(T, n, int(off), N, x0_dev) for n, off in zip(sizes, offsets[:-1])]
+    rng = np.random.default_rng(5)
+    for kind in (1, 6, 3):  # a range of e^40, a fifth of the costs infinite (both free of ties at these k), plateaus (tied)
+        costs = topk_cost_vector(rng, N, kind)
+        lam = _temperature_for(costs)
+        ref = _host_softmax(costs, lam)
+        order_all = np.lexsort((np.arange(N), costs))
+        c = torch.from_numpy(costs).cuda()
+        for k in (300, 1025):
+            free = tie_free(costs, order_all[:k], k)
+            assert free == (kind != 3), (kind, k)  # (numpy alone, for the seed above)
+            out_full, w_full = _top_samples_of(full, c, k, lam)
+            sums, words = [], []
+            for sol, n, off in zip(shards, sizes, offsets[:-1]):
+                cs = c[off:off + n].contiguous()
+                words.append(_top_candidates_of(sol._h, cs, k, sol._stream()))
+                sums.append(_summary(sol, lam))
+            merged = np.sort(np.concatenate(words))[:k]  # (uint64: unsigned order)
+            best = torch.from_numpy(merged.view(np.int64).copy()).cuda()
+            allsum = torch.stack(sums).contiguous()
+            s0, st = shards[0], shards[0]._stream()
+            a = torch.empty(T, 1, device="cuda")
+            s0._h.call("mppi_finalize", C.c_void_p(allsum.data_ptr()), 3, lam, 0, a.data_ptr(), None, None, st)
+            out, w = torch.empty(k, T + 1, 2, device="cuda"), torch.empty(k, device="cuda")
+            s0._h.call("mppi_rollout_candidates", best.data_ptr(), k, lam, out.data_ptr(), w.data_ptr(), st)
+            got, got_full = w.cpu().numpy(), w_full.cpu().numpy()
+            for name, v in (("merged", got), ("unsharded", got_full)):
+                err = np.abs(v - ref[order_all[:k]]).max()
+                print(f"sharded top-k kind={kind} k={k}: {name} weights off by {err / ref.max():.2e} of the largest")
+                assert np.all(np.isfinite(v)) and np.all(np.diff(v) <= 0) and err <= 2e-5 * ref.max(), (kind, k, name)
+            assert np.abs(got - got_full).max() <= 2e-5 * got_full.max(), (kind, k)
+            if free:
+                assert np.array_equal(merged & np.uint64(0xFFFFFFFF), order_all[:k].astype(np.uint64)), (kind, k)
+                assert torch.equal(out, out_full), (kind, k)
+            assert torch.equal(out[:, 0, :], x0_dev.expand(k, 2))
+    # injected noise cannot be regenerated for another shard's samples
+    inj, _ = make_solver("pendulum", T, 4097, lambda_=1.0)
+    inj.inject_noise(torch.zeros(4097, T, 1))
+    inj.forward(x0)
+    words = torch.from_numpy(merged[:8].view(np.int64).copy()).cuda()
+    out, w = torch.empty(8, T + 1, 2, device="cuda"), torch.empty(8, device="cuda")
+    with pytest.raises(_capi.MppiError, match=r"mppi_rollout_candidates failed \(-3\)"):  # MPPI_E_STATE
+        inj._h.call("mppi_rollout_candidates", words.data_ptr(), 8, 1.0, out.data_ptr(), w.data_ptr(), inj._stream())
 
 
 def test_row_pool_steps_aside_under_stream_capture():
