@@ -101,7 +101,7 @@ typedef struct MppiConfig {
 const char* mppi_version(void);
 /* Integer version of THIS header's function signatures; bindings compare it with the constant they were written
  * against and refuse a stale library (a changed argument list would otherwise be called with shifted arguments). */
-#define MPPI_ABI_VERSION 10
+#define MPPI_ABI_VERSION 11
 int mppi_abi_version(void);
 /* Number of visible HIP devices (0 => the product cannot run; callers must fail loudly). */
 int mppi_device_count(void);
@@ -115,7 +115,8 @@ int mppi_destroy(mppi_handle_t h);
 /* `u_min`, `u_max`, `sigmas` constructor tensors (mppi.py:32-34,96-98,109-121) as host arrays of n = dim_control
  * values: replaces the bounds / noise scales taken from MppiConfig.  REQUIRED once, before the first sample, for
  * generic handles with dim_control > MPPI_MAX_DIM_CONTROL (the config arrays hold four); native models accept it
- * only before mppi_set_model_params.  Synchronises. */
+ * only before mppi_set_model_params.  The per-step sigma table of the covariance adaptation (mppi_get_sigma_table) starts over
+ * from the new `sigmas`, adapted or not, and noise tiles already drawn from the old values are dropped.  Synchronises. */
 int mppi_set_control_limits(mppi_handle_t h, const float* u_min_host, const float* u_max_host, const float* sigmas_host,
                             int n);
 
@@ -256,6 +257,37 @@ int mppi_set_auto_lambda(mppi_handle_t h, int rule, double param, double lam_min
  * per solve and no host synchronisation for any temperature rule. */
 int mppi_solve(mppi_handle_t h, const float* x0_dev, uint32_t solve_idx, float lambda, float* action_out_dev,
                float* state_seq_out_dev, float* stats_out_dev, void* stream);
+/* Covariance adaptation of the sampling noise — the capability the reference sketches, commented out, at mppi.py:400-418
+ * (after https://arxiv.org/abs/2104.00241): after the weights of a solve the diagonal covariance
+ *   var[t][k] = sum_i w_i * (U_i[t][k] - ubar[t][k])^2,   w_i = e_i / sum e (the weights of mppi_weights_reduce, same fp32
+ *   expression), U_i = the clamped perturbed actions of that solve (exploration samples included), ubar = A / sum e (the
+ *   weighted mean of mppi.py:381-385, before the Savitzky-Golay step)
+ * moves a per-step table of standard deviations s[T][dc], from which the NEXT solve draws eps[i][t][k] = z * s[t][k] (z: the
+ * Philox / Box-Muller normal every solve draws; only the factor changes):
+ *   s^2[t][k] <- (1 - rate) * s^2[t][k] + rate * (var[t][k] + floor),   then s clamped into [sigma_min[k], sigma_max[k]].
+ * rate = 1, floor = 1e-6 (`small_cov`, mppi.py:408-411), no clamp is the sketch, literally.  Off by default: nothing changes
+ * for a handle that never switches it on.  While it is on the noise is always materialised as tiles (the handle behaves like
+ * "noise_regen" = 0 whatever the option says; the single launch of small problems regenerates noise, so mppi_solve takes
+ * the multi-kernel sequence) and mppi_sample_posterior draws with the table too (mppi.py:416-418: `_noise_distribution`
+ * follows the covariance).  Not available for sharded handles (options "exchange_p2p" / "exchange_comm": the variance would
+ * need a second exchange).
+ *   mppi_set_covariance_adaptation  mppi.py:400-418 on / off with 0 <= rate <= 1, floor >= 0 and the clamp
+ *                         sigma_min_host / sigma_max_host [dim_control] (NULL: 0 / +inf).  Leaves the table as it is.
+ *                         Set-up path: synchronises.
+ *   mppi_update_covariance  mppi.py:402-411 for the solve in flight, as two launches on `stream` (the weighted second moment
+ *                         over the live tiles as per-block partial rows; their fold in a fixed order and the update: no
+ *                         atomics, the table is bit-reproducible).  Call it BETWEEN mppi_weights_reduce and mppi_finalize,
+ *                         with the same lambda: it needs the mean that solve sampled around, which mppi_finalize
+ *                         replaces.  mppi_solve does so itself while the adaptation is on.  A voided solve (NaN weights
+ *                         after a temperature search that timed out) leaves the table unchanged.
+ *   mppi_get_sigma_table / mppi_set_sigma_table  the table (`_covariance` of mppi.py:411 as standard deviations) as [T][dc]
+ *                         floats, device or host; filled from `sigmas` by mppi_create / mppi_set_control_limits, copied by
+ *                         mppi_clone_state with the settings.  Host copies out synchronise. */
+int mppi_set_covariance_adaptation(mppi_handle_t h, int enable, float rate, float floor, const float* sigma_min_host,
+                                   const float* sigma_max_host);
+int mppi_update_covariance(mppi_handle_t h, float lambda /* > 0, or MPPI_LAMBDA_DEVICE */, void* stream);
+int mppi_get_sigma_table(mppi_handle_t h, float* table_out, int on_device, void* stream);
+int mppi_set_sigma_table(mppi_handle_t h, const float* table, int on_device, void* stream);
 /* Lazily completed state sequences (mppi_set_option("lazy_state_seq", 1)).  The reference returns `state_seq` — the batch-1
  * rollout of the solution, mppi.py:448-449,508-524 — with the action sequence, but nothing on a control loop's critical
  * path needs it: the next solve samples around the mean, env.step applies a[0].  With the option set, mppi_finalize /

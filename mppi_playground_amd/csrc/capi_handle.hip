@@ -171,6 +171,9 @@ int mppi_create(const MppiConfig* cfg, mppi_handle_t* out) {
         h->limits_set = false;
         if (md.dc <= MPPI_MAX_DIM_CONTROL)  // the config arrays hold all of it (dim_control = 3)
             if (int rc = mppi_set_control_limits(h, cfg->u_min, cfg->u_max, cfg->sigmas, md.dc)) return rc;
+    } else {  // the per-step sigma table of the covariance adaptation (wide handles: the sigma section of coltab)
+        HIP_TRY(h, h->cov.sigtab.alloc(4 * (size_t)d.R));
+        if (int rc = fill_sigma_table(h, cfg->sigmas, md.dc)) return rc;
     }
     if (int rc = mpo_upload(h, 1.0, 0.1, 0.2, false)) return rc;  // mppi.py:191-200
     HIP_TRY(h, hipDeviceGetAttribute(&h->cu_count, hipDeviceAttributeMultiprocessorCount, cfg->device));
@@ -201,6 +204,9 @@ int mppi_set_control_limits(mppi_handle_t h, const float* u_min, const float* u_
         HIP_TRY(h, hipDeviceSynchronize());
         HIP_TRY(h, hipMemcpy(h->core.coltab, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
         h->limits_set = true;
+        h->core.tiles_valid = h->core.tiles_valid && h->core.injected;
+    } else {  // (the per-step sigma table starts over from the new `sigmas`: an adapted table is reset, tiles drawn from it are stale)
+        if (int rc = fill_sigma_table(h, sigmas, n)) return rc;
         h->core.tiles_valid = h->core.tiles_valid && h->core.injected;
     }
     return MPPI_OK;
@@ -240,6 +246,12 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
     dc.x0_cur = dc.x0;
     CLONE(core.x0_used);
     CLONE(core.coltab);
+    CLONE(cov.sigtab);
+    if (src->cov.on) {  // covariance adaptation: the settings (the table itself is one of the two buffers above)
+        if (int rc = cov_alloc(dst)) return rc;
+        CLONE(cov.lim);
+    }
+    dst->cov.on = src->cov.on; dst->cov.rate = src->cov.rate; dst->cov.floor = src->cov.floor; dst->cov.ready = false;
     CLONE(core.mean);
     CLONE(core.mean_used);
     CLONE(reduce.solve_stats);
@@ -366,6 +378,8 @@ int mppi_set_option(mppi_handle_t h, const char* key, int64_t value) {
     if (k == "search_rearm") { h->search.error.clear(); return MPPI_OK; }
     if (k == "essps_merge0") { o.essps_merge0 = value != 0; return MPPI_OK; }  // A/B: round 0 of the ESSPS chain as one launch
     if (k == "fold_path") { o.fold_mode = (value >= 0 && value <= 2) ? (int)value : 0; return MPPI_OK; }
+    if ((k == "exchange_p2p" || k == "exchange_comm") && value && h->cov.on)
+        return fail(h, MPPI_E_INVALID, "covariance adaptation is not available for sharded solves (the variance would need a second exchange)");
     if (k == "exchange_p2p") {  // sharded solves: summaries travel through the peer-to-peer buffer, no collective
         if (value && !h->xchg.p2p_connected) return fail(h, MPPI_E_STATE, "exchange_p2p: call mppi_p2p_alloc / mppi_p2p_connect first");
         h->xchg.p2p_enabled = value != 0;
@@ -376,7 +390,11 @@ int mppi_set_option(mppi_handle_t h, const char* key, int64_t value) {
         h->xchg.comm_enabled = value != 0;
         return MPPI_OK;
     }
-    if (k == "noise_regen") { o.noise_regen = value ? 1 : 0; h->core.tiles_valid = h->core.tiles_valid && h->core.injected; return MPPI_OK; }
+    if (k == "noise_regen") {  // (under covariance adaptation the tiles are the noise whatever this says: they stay)
+        o.noise_regen = value ? 1 : 0;
+        h->core.tiles_valid = h->core.tiles_valid && (h->core.injected || h->cov.on);
+        return MPPI_OK;
+    }
     return fail(h, MPPI_E_INVALID, "unknown option " + k);
 }
 

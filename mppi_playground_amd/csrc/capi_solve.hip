@@ -91,7 +91,7 @@ static bool fold_fits(mppi_handle_t h) {
 static int materialize_tiles(mppi_handle_t h, hipStream_t s) {
     const unsigned grid = (unsigned)((h->d.tiles + 3) / 4);
     if (!h->limits_set) return fail(h, MPPI_E_STATE, "dim_control > 4: call mppi_set_control_limits first");
-    if (h->wide) hipLaunchKernelGGL(sample_kernel<true>, dim3(grid), dim3(BLOCK), 0, s, h->core.noise, h->d, h->core.gen, h->core.coltab);
+    if (h->wide || h->cov.on) hipLaunchKernelGGL(sample_kernel<true>, dim3(grid), dim3(BLOCK), 0, s, h->core.noise, h->d, h->core.gen, (const float*)sigma_table(h));
     else hipLaunchKernelGGL(sample_kernel<false>, dim3(grid), dim3(BLOCK), 0, s, h->core.noise, h->d, h->core.gen, (const float*)nullptr);
     HIP_TRY(h, hipGetLastError());
     h->core.tiles_valid = true;
@@ -105,7 +105,7 @@ int need_tiles(mppi_handle_t h, hipStream_t s) {
 }
 
 // lambda argument of the reduce / finalize entry points -> (launch constant, device pointer or null)
-static int resolve_lambda(mppi_handle_t h, float lambda, const float** lam_dev) {
+int resolve_lambda(mppi_handle_t h, float lambda, const float** lam_dev) {
     *lam_dev = nullptr;
     if (lambda == MPPI_LAMBDA_DEVICE) {
         if (!h->search.lambda_dev_valid) return fail(h, MPPI_E_STATE, "MPPI_LAMBDA_DEVICE: no temperature on the device (run a device-resident rule or mppi_mpo_reset first)");
@@ -157,7 +157,7 @@ static bool fused_applies(mppi_handle_t h, float lambda) {
     // (the single launch searches LBPS on 32-temperature grids; the reference's Brent search is a kernel of its own)
     if (lambda == MPPI_LAMBDA_DEVICE && h->search.auto_rule == MPPI_AUTO_LBPS && !h->opt.lbps_grid) return false;
     if (h->opt.fused_mode == 1 && h->d.N > (search ? FUSED_AUTO_MAX_SAMPLES_SEARCH : FUSED_AUTO_MAX_SAMPLES)) return false;
-    if (!(h->opt.noise_regen && !h->core.injected && !h->wide)) return false;         // the noise is regenerated in registers
+    if (!regen_noise(h)) return false;                                                // the noise is regenerated in registers
     if (h->xchg.p2p_enabled || h->xchg.comm_enabled) return false;                      // sharded solves exchange between devices
     if (h->d.row > FUSED_MAX_ROW) return false;
     if (h->d.N > (int64_t)FUSED_BLOCK * std::min(FUSED_MAX_BLOCKS, h->cu_count)) return false;  // every block must be resident at once
@@ -259,7 +259,7 @@ int mppi_sample(mppi_handle_t h, uint32_t solve_idx, void* stream) {
     h->core.gen.solve_idx = solve_idx;
     h->core.injected = false;
     h->core.tiles_valid = false;
-    if (h->opt.noise_regen && !h->wide) return MPPI_OK;  // consumers regenerate eps(seed, solve, i, t, k) in registers
+    if (h->opt.noise_regen && !h->wide && !h->cov.on) return MPPI_OK;  // consumers regenerate eps(seed, solve, i, t, k) in registers
     StageTimer tm(h, 0, s);
     return materialize_tiles(h, s);
 }
@@ -317,7 +317,7 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
         return MPPI_OK;
     }
     StageTimer tm(h, 1, s);
-    const bool gen = h->opt.noise_regen && !h->core.injected;
+    const bool gen = h->opt.noise_regen && !h->core.injected && !h->cov.on;
     if (!gen && !h->core.tiles_valid) return fail(h, MPPI_E_STATE, "no noise: call mppi_sample or mppi_inject_noise first");
     h->seq.min_slot ^= 1;
     unsigned* mk = h->core.min_key + h->seq.min_slot;
@@ -384,7 +384,7 @@ int mppi_weights_reduce(mppi_handle_t h, float lambda, float* summary_out_dev, v
     blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, REDUCE_MAX_BLOCKS));
     h->reduce.last_reduce_blocks = (int)blocks;
     const dim3 grid((unsigned)blocks, (unsigned)h->reduce.nchunks);
-    const bool gen = h->opt.noise_regen && !h->core.injected && !h->wide;
+    const bool gen = regen_noise(h);
     if (!gen && !h->core.tiles_valid) return fail(h, MPPI_E_STATE, "no noise: call mppi_sample or mppi_inject_noise first");
     const unsigned* mk = h->core.min_key + h->seq.min_slot;
 #define CALL_REDUCE(GPWV, GENV, WIDEV, CHAINSV, REMV)                                                 \
@@ -415,7 +415,8 @@ int mppi_weights_reduce(mppi_handle_t h, float lambda, float* summary_out_dev, v
     const bool many_rows = h->opt.fold_mode == 0 ? *(volatile int*)h->reduce.live_hint.host > FOLD_IN_FINALIZE_MAX_ROWS : h->opt.fold_mode == 2;
     const bool comm = h->xchg.comm_enabled && !h->xchg.p2p_enabled;
     if (comm && summary_out_dev) return fail(h, MPPI_E_INVALID, "exchange_comm: the library gathers the summaries itself (pass NULL)");
-    if (summary_out_dev || h->xchg.p2p_enabled || comm || !fold_fits(h) || many_rows) {
+    // (covariance adaptation: the step between this call and mppi_finalize reads the summary)
+    if (summary_out_dev || h->xchg.p2p_enabled || comm || !fold_fits(h) || many_rows || h->cov.on) {
         const unsigned sgrid = (unsigned)((h->reduce.colsp + SUM_COLS - 1) / SUM_COLS + 1);
         hipLaunchKernelGGL(summarize_kernel, dim3(sgrid), dim3(SUM_BLOCK), 0, s, h->reduce.partials, h->reduce.heads, mk, (int)blocks,
                            h->reduce.colsp, h->d.row, h->reduce.summary, comm ? h->xchg.comm_send : summary_out_dev, h->reduce.live_hint.dev, p2p);
@@ -424,6 +425,7 @@ int mppi_weights_reduce(mppi_handle_t h, float lambda, float* summary_out_dev, v
     }
     if (comm)  // the solve's only exchange: 4 + T*dc floats per rank, on the solve's own stream
         RCCL_TRY(h, rccl().all_gather(h->xchg.comm_send, h->xchg.comm_recv, (size_t)(MPPI_SUMMARY_HEAD + h->d.row), ncclFloat, h->xchg.comm, s));
+    h->cov.ready = h->cov.on;
     return MPPI_OK;
 }
 
@@ -473,6 +475,7 @@ int mppi_finalize(mppi_handle_t h, const float* summaries_dev, int num_shards, f
 #undef CALL_FINALIZE
     }
     HIP_TRY(h, hipGetLastError());
+    h->cov.ready = false;  // (a stored warm start is no longer the mean this solve sampled around)
     ++h->lazy.finalize_serial;
     if (defer) { h->lazy.pending_out = state_out; h->lazy.pending_serial = h->lazy.finalize_serial; h->lazy.pending_stream = s; }
     return MPPI_OK;
@@ -533,6 +536,7 @@ int mppi_solve(mppi_handle_t h, const float* x0_dev, uint32_t solve_idx, float l
                                   : mppi_lbps_brent_device(h, h->search.auto_param, h->search.auto_lo, h->search.auto_hi, stream)) return rc;
     }
     if (int rc = mppi_weights_reduce(h, lambda, nullptr, stream)) return rc;
+    if (h->cov.on) { if (int rc = mppi_update_covariance(h, lambda, stream)) return rc; }
     if (int rc = mppi_finalize(h, nullptr, 1, lambda, 1, action_out_dev, state_seq_out_dev, stats_out_dev, stream)) return rc;
     // MPO: the dual steps after every solve, whatever temperature this solve's weights were given (mppi.py:387-398)
     if (h->search.auto_rule == MPPI_AUTO_MPO) return mppi_mpo_step_device(h, stream);

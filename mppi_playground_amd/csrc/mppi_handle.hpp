@@ -14,12 +14,14 @@
 //   capi_search.hip    softmax statistics, ESSPS / LBPS / Brent / MPO               (+ the non-template search kernels)
 //   capi_topk.hip      queries after a solve                                         (mppi_topk.hpp)
 //   capi_exchange.hip  RCCL loader, comm / p2p exchanges, time-out flags             (+ the p2p kernels)
+//   capi_covariance.hip  covariance adaptation: settings, the per-step sigma table, the step after the weights (mppi_variance.hpp)
 // Kernel headers, one per stage.  A kernel that is not a template is defined in the one unit that launches it.
 //   mppi_common.hpp    Dims, GenCtx, wave reductions
 //   mppi_cells.hpp     the tagged 8-byte cell: how blocks of one launch and peer devices hand values over (search, fused, exchange)
 //   mppi_sample.hpp    step 1: the noise stream (gen_noise4), sample_kernel, posterior draws
 //   mppi_rollout.hpp   steps 1b-3: rollout_cost_kernel (THE hot loop: trajectory_cost), the wavefront-per-trajectory variant
 //   mppi_reduce.hpp    steps 5-6: weights_reduce_kernel
+//   mppi_variance.hpp  after steps 5-6, opt-in: weighted_variance_kernel, sigma_update_kernel (mppi_covariance.hpp: the scalar rule)
 //   mppi_exchange.hpp  sharded solves: peer-to-peer buffers
 //   mppi_finalize.hpp  finalize_kernel (combine, normalise, SG filter, warm start, batch-1 rollout)
 //   mppi_search.hpp    step 4 on the device: statistics, ESSPS / LBPS / MPO
@@ -182,6 +184,18 @@ struct MppiSolver {
         DevBuf<float> sg_history;      // [T-1][dc] `_actions_history_for_sg` (mppi.py:160-166,441-443)
         int sg_window = 0;
     } reduce;
+
+    // covariance adaptation (the sketch at mppi.py:400-418; capi_covariance.hip).  While `on`, the noise is drawn per COLUMN
+    // from the sigma table and always materialised as tiles (the handle behaves like noise_regen = 0).
+    struct Cov {
+        bool on = false;
+        float rate = 1.0f, floor = 1e-6f;
+        DevBuf<float> sigtab;          // per-column sigma [4R], zeros past the row (wide handles: the sigma section of core.coltab)
+        DevBuf<float> lim;             // {sigma_min[dc], sigma_max[dc]}
+        DevBuf<float> part;            // [REDUCE_MAX_BLOCKS][colsp] partial rows of weighted_variance_kernel
+        DevBuf<float> live;            // [REDUCE_MAX_BLOCKS] which of them were published
+        bool ready = false;            // mppi_weights_reduce ran and mppi_finalize has not yet: the step may run
+    } cov;
 
     // temperature: statistics passes, the device-resident ESSPS / LBPS / Brent / MPO searches
     struct Search {
@@ -434,7 +448,17 @@ void refresh_pad(mppi_handle_t h, hipStream_t s);
 int prepare_map(mppi_handle_t h, int slot, int nx, int ny, float cell, float ox, float oy);
 int reserve_ref(mppi_handle_t h, int rows);
 
+// the per-column sigma table the sampler reads (see MppiSolver::Cov)
+inline float* sigma_table(mppi_handle_t h) { return h->wide ? h->core.coltab.p : h->cov.sigtab.p; }
+// regenerate the noise in registers?  Not when it was injected, nor when sigma comes per column from a table
+inline bool regen_noise(mppi_handle_t h) { return h->opt.noise_regen && !h->core.injected && !h->wide && !h->cov.on; }
+
+// capi_covariance.hip
+int cov_alloc(mppi_handle_t h);
+int fill_sigma_table(mppi_handle_t h, const float* sigmas, int n);
+
 // capi_solve.hip
+int resolve_lambda(mppi_handle_t h, float lambda, const float** lam_dev);
 int need_tiles(mppi_handle_t h, hipStream_t s);
 int flush_state_seq(mppi_handle_t h, hipStream_t s);
 // Before anything that changes which kernel variant MPPI_DISPATCH picks or what the model context holds (math level,

@@ -262,3 +262,35 @@ def sg_filter_sequence(history: np.ndarray, action_seq: np.ndarray, coeffs: np.n
     for i in range(prolonged.shape[1]):
         out[:, i] = apply_savitzky_golay(prolonged[:, i], coeffs)
     return out[-T:]
+
+
+def check_covariance_args(adapt_covariance, cov_rate, cov_floor, sigma_min, sigma_max, dim_control, shard_samples,
+                          noise_source):
+    """Validate the covariance-adaptation keyword arguments of MPPI (the sketch at src/pi_mpc/mppi.py:400-418) and return
+    (cov_rate, cov_floor, sigma_min[dc], sigma_max[dc]) as floats / float32 arrays (defaults 0 and +inf).  ValueError for a
+    rate outside [0, 1], a negative floor, sigma_min > sigma_max (or negative) in any dimension, and for the two
+    combinations the adaptation does not support."""
+    rate, floor = float(cov_rate), float(cov_floor)
+    if not 0.0 <= rate <= 1.0:
+        raise ValueError(f"cov_rate must lie in [0, 1], got {cov_rate}")
+    if not (floor >= 0.0 and np.isfinite(floor)):
+        raise ValueError(f"cov_floor must be >= 0, got {cov_floor}")
+
+    def vec(v, default):
+        if v is None:
+            return np.full(dim_control, default, np.float32)
+        a = np.asarray(v.detach().cpu() if hasattr(v, "detach") else v, dtype=np.float32).reshape(-1)
+        if a.shape != (dim_control,):
+            raise ValueError(f"sigma_min / sigma_max must have shape ({dim_control},)")
+        return a
+
+    smin, smax = vec(sigma_min, 0.0), vec(sigma_max, np.inf)
+    if not (np.all(smin >= 0.0) and np.all(smin <= smax)):
+        raise ValueError("need 0 <= sigma_min <= sigma_max in every control dimension")
+    if adapt_covariance and shard_samples:
+        raise ValueError("adapt_covariance=True is not available with shard_samples=True: the weighted variance would need "
+                         "a second exchange between the shards")
+    if adapt_covariance and noise_source == "torch_cpu":
+        raise ValueError("adapt_covariance=True is not available with noise_source='torch_cpu': every draw would need the "
+                         "sigma table on the host")
+    return rate, floor, smin, smax

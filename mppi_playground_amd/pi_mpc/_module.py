@@ -20,7 +20,7 @@ class ModuleProtocolMixin:
         """A second solver that continues EXACTLY like this one: same constructor arguments, a handle of its own, and every
         piece of dynamic state copied on the device (mppi_clone_state: warm start, noise identity, the last solve's costs,
         Savitzky-Golay history, the temperature and the device-resident search / dual state, model parameters, maps,
-        reference window and path index, options) or on the host (RNG stream position, the torch-CPU generator, temperatures
+        reference window and path index, options, the sigma table and settings of the covariance adaptation) or on the host (RNG stream position, the torch-CPU generator, temperatures
         already fetched).  The callables are deep-copied like the reference's attributes would be — with them the environment
         / controller objects that own the model's parameters — and the native tags re-resolved on the copies."""
         if self._world > 1 or self._force_exchange:
@@ -84,7 +84,7 @@ class ModuleProtocolMixin:
     def get_extra_state(self) -> Dict[str, Any]:
         """The solver's dynamic state for state_dict() (entry `_extra_state`; the reference keeps the same things as plain
         attributes, which its state_dict() silently drops): warm start, Savitzky-Golay history, RNG stream position (Philox
-        solve index and the torch-CPU generator), the temperature and — MPO — the dual with its Adam moments."""
+        solve index and the torch-CPU generator), the adapted sigma table (adapt_covariance), the temperature and — MPO — the dual with its Adam moments."""
         if self._lambda_pending:
             self._fetch_lambda()
         mean = torch.empty(self._horizon, self._dim_control, device=self._device, dtype=self._dtype)
@@ -93,6 +93,8 @@ class ModuleProtocolMixin:
                "sg_history": torch.from_numpy(np.array(self._actions_history_for_sg, copy=True)),
                "solve_idx": int(self._solve_idx), "lambda": self._lambda_value, "last_lambda": self._last_lambda_value,
                "cpu_generator": None if self._cpu_gen is None else self._cpu_gen.get_state(), "mpo": None}
+        if self._adapt_covariance:  # the adapted per-step standard deviations
+            out["sigma_seq"] = self.sigma_seq.cpu()
         if self._auto_lambda == "MPO":
             if self._rule_on_device == "MPO":
                 st4 = (C.c_double * 4)()
@@ -114,6 +116,14 @@ class ModuleProtocolMixin:
                                f"dim_control {self._dim_control}")
         self.set_warm_start(a.numpy(), sg_history=state["sg_history"].numpy())
         self._solve_idx = int(state["solve_idx"])
+        if state.get("sigma_seq") is not None and self._adapt_covariance:
+            sg = state["sigma_seq"]
+            if tuple(sg.shape) != (self._horizon, self._dim_control):
+                raise RuntimeError(f"sigma_seq of shape {tuple(sg.shape)} does not fit horizon {self._horizon} x "
+                                   f"dim_control {self._dim_control}")
+            sg = sg.to(self._device, self._dtype).contiguous()
+            self._h.call("mppi_set_sigma_table", sg.data_ptr(), 1, self._stream())
+            torch.cuda.current_stream(self._device).synchronize()
         if state.get("cpu_generator") is not None and self._cpu_gen is not None:
             self._cpu_gen.set_state(state["cpu_generator"])
         if state.get("mpo") is not None and self._auto_lambda == "MPO":

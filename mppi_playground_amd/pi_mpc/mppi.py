@@ -86,6 +86,11 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         sg_filter: str = "device",
         graph_callables: bool = False,
         lazy_state_seq: Optional[bool] = None,
+        adapt_covariance: bool = False,
+        cov_rate: float = 1.0,
+        cov_floor: float = 1e-6,
+        sigma_min: Optional[torch.Tensor] = None,
+        sigma_max: Optional[torch.Tensor] = None,
         _force_exchange: bool = False,
     ) -> None:
         """Arguments up to `seed` are the reference's (src/pi_mpc/mppi.py:24-47).
@@ -138,6 +143,18 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                 returned buffer holds NaN (a reader that bypasses torch — a raw data_ptr(), another library — must call
                 `join_state_seq()` first; a completion on another stream is ordered behind the solve's stream).  For
                 control loops that do not look at `state_seq` every tick (bench.py passes True and says so in its line).
+            adapt_covariance: OPT-IN (default False: `sigmas` for the whole horizon, every solve, bit for bit as before).  True:
+                the capability the reference sketches, commented out, at mppi.py:400-418 — after every solve the diagonal
+                covariance of the weighted samples, var[t,k] = sum_i w_i (U_i[t,k] - ubar[t,k])^2 (U: the clamped perturbed
+                actions, exploration samples included; ubar: the weighted mean before the Savitzky-Golay step), moves a
+                per-step table s[T, dim_control] (`sigma_seq`) and the next solve draws eps[i,t,k] = z * s[t,k] from it:
+                s^2 <- (1 - cov_rate) * s^2 + cov_rate * (var + cov_floor), then s clamped into [sigma_min, sigma_max].
+                cov_rate (in [0, 1]) = 1 and cov_floor (>= 0) = 1e-6 (`small_cov`) with no clamp are the sketch, literally;
+                cov_rate = 0 never moves.  sigma_min / sigma_max: optional [dim_control] tensors (defaults 0 / +inf).
+                get_samples_from_posterior draws with the current table, reset() puts it back to `sigmas`, deepcopy and
+                state_dict() carry it.  The noise is then always materialised (like set_option("noise_regen", 0)) and small
+                problems take the multi-kernel path.  Not with shard_samples=True (the variance would need a second
+                exchange) or noise_source="torch_cpu" (every draw would need the table on the host): ValueError.
             shard_samples: treat `num_samples` as the GLOBAL sample count and let this rank own the
                 contiguous block rank*N/W .. (rank+1)*N/W of it (torch.distributed must be
                 initialised); the 4+T*dc-float shard summaries are exchanged once per solve with one RCCL
@@ -158,12 +175,17 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                           dtype=dtype, seed=seed, noise_source=noise_source, shard_samples=shard_samples,
                           process_group=process_group, auto_lambda_stats=auto_lambda_stats, essps_search=essps_search,
                           lbps_search=lbps_search, recognize_closures=recognize_closures, sg_filter=sg_filter,
-                          graph_callables=graph_callables, lazy_state_seq=lazy_state_seq, _force_exchange=_force_exchange)
+                          graph_callables=graph_callables, lazy_state_seq=lazy_state_seq, adapt_covariance=adapt_covariance,
+                          cov_rate=cov_rate, cov_floor=cov_floor, sigma_min=sigma_min, sigma_max=sigma_max,
+                          _force_exchange=_force_exchange)
         assert u_min.shape == (dim_control,)
         assert u_max.shape == (dim_control,)
         assert sigmas.shape == (dim_control,)
         if dtype != torch.float32:
             raise ValueError("the HIP path computes in float32 (the reference default dtype)")
+        self._adapt_covariance = bool(adapt_covariance)
+        self._cov_rate, self._cov_floor, self._sigma_min, self._sigma_max = _host.check_covariance_args(
+            adapt_covariance, cov_rate, cov_floor, sigma_min, sigma_max, dim_control, shard_samples, noise_source)
         dev = torch.device(device)
         if dev.type != "cuda":
             raise ValueError(f"device={dev}: this MPPI runs its hot path on MI355X only; there is no CPU path "
@@ -312,6 +334,10 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         if dim_control > _capi.MAX_DIM_CONTROL:  # the config holds four controls: hand over the full vectors
             f = lambda t: (C.c_float * dim_control)(*[float(v) for v in t])  # noqa: E731
             self._h.call("mppi_set_control_limits", f(u_min), f(u_max), f(sigmas), dim_control)
+        if self._adapt_covariance:  # (after the limits: the table starts from `sigmas`)
+            f = lambda a: (C.c_float * dim_control)(*[float(v) for v in a])  # noqa: E731
+            self._h.call("mppi_set_covariance_adaptation", 1, self._cov_rate, self._cov_floor, f(self._sigma_min),
+                         f(self._sigma_max))
         # the LBPS search and the MPO step run inside the library (no interpreter work per probe) whenever the
         # statistics come from this device alone; sharded solvers combine the shards' statistics in Python
         self._search_in_library = auto_lambda_stats == "device" and self._world == 1
@@ -623,6 +649,17 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         self._actions_history_for_sg = np.zeros((self._horizon - 1, self._dim_control), np.float32)
         self._essps_prev = None  # the next ESSPS search starts cold (no grid clustered around the last temperature)
         self._h.call("mppi_set_option", b"essps_cold", 1)
+        if self._adapt_covariance:  # the adapted table goes back to the constructor's `sigmas`
+            self._sigma_seq_reset = self._sigmas.repeat(self._horizon, 1).contiguous()  # (alive until the copy ran)
+            self._h.call("mppi_set_sigma_table", _ptr(self._sigma_seq_reset), 1, self._stream())
+
+    @property
+    def sigma_seq(self) -> torch.Tensor:
+        """The standard deviations the next solve draws its noise with, [T, dim_control] on the device (a copy): `sigmas`
+        for every step unless adapt_covariance moves them (`_covariance` of the sketch at mppi.py:411, as its square root)."""
+        out = torch.empty(self._horizon, self._dim_control, device=self._device, dtype=self._dtype)
+        self._h.call("mppi_get_sigma_table", _ptr(out), 1, self._stream())
+        return out
 
     @property
     def _actions_history_for_sg(self) -> np.ndarray:
@@ -842,6 +879,12 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             self._gathered = torch.empty(self._world, self._summary.numel(), device=self._device, dtype=self._dtype)
         return all_gather_summaries(self._summary, self._pg, out=self._gathered), self._world
 
+    def _covariance_step(self, lam, st) -> None:
+        """The sketch at src/pi_mpc/mppi.py:400-418 (adapt_covariance): weighted variance of this solve's clamped actions ->
+        the sigma table of the next solve.  Needs the mean this solve sampled around, so it runs before _finalize."""
+        if self._adapt_covariance:
+            self._h.call("mppi_update_covariance", lam, st)
+
     def _finalize(self, summaries, nsh, lam, st, native: bool) -> None:
         """Steps 6-8 (src/pi_mpc/mppi.py:381-385,448-452): normalise, warm start, batch-1 rollout — into fresh output tensors
         (the kernel writes straight into what is returned)."""
@@ -880,6 +923,7 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         self._h.call("mppi_rollout_cost", st)  # Steps 1b-3: clamp, rollout, costs (src/pi_mpc/mppi.py:266-336)
         lam = self._temperature(st)
         summaries, nsh = self._reduce_and_exchange(lam, st)
+        self._covariance_step(lam, st)
         self._finalize(summaries, nsh, lam, st, native=True)
         self._mpo_after_weights(st)
         if self._host_sg:
@@ -897,6 +941,7 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         self._generic_rollout_costs(state, info)  # Steps 1b-3 with the callables; the summed costs go back to the library
         lam = self._temperature(st)
         summaries, nsh = self._reduce_and_exchange(lam, st)
+        self._covariance_step(lam, st)  # after the library reduction, before the warm start replaces this solve's mean
         self._finalize(summaries, nsh, lam, st, native=False)
         self._mpo_after_weights(st)
         if self._host_sg:
