@@ -491,8 +491,10 @@ int mppi_p2p_error(mppi_handle_t h);
  * (statistics pass + select step; round 1 always is: it returns at once when round 0 finished the search) — same
  * temperature to the bit, measured no faster (default 0); "timing" (see mppi_get_timing). */
 int mppi_set_option(mppi_handle_t h, const char* key, int64_t value);
-/* Device time per stage from HIP event pairs recorded on the caller's stream around every stage call
- * since the last drain (no host synchronisation while recording): out[0..3] = mean ms of
+/* Device time per stage from HIP event pairs since the last drain (no host synchronisation while recording).  The
+ * events ride on the stage's own dispatches: a stage time runs from the begin of its first kernel to the end of its
+ * last, without the wait between a stream marker and the dispatch (a captured stream, and a stage that ends in a
+ * collective, keep plain event records).  out[0..3] = mean ms of
  * {sample, rollout_cost, weights_reduce, finalize}, out[4..7] = number of calls averaged.
  * Enabled by mppi_set_option(h, "timing", 1).  Synchronises and clears the recorded pairs. */
 int mppi_get_timing(mppi_handle_t h, float* out_ms8);

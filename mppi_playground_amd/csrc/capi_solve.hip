@@ -88,11 +88,12 @@ static bool fold_fits(mppi_handle_t h) {
     return finalize_lds_floats(h, 1, 255 /* widest filter */, true) * sizeof(float) <= 64 * 1024;
 }
 
-static int materialize_tiles(mppi_handle_t h, hipStream_t s) {
+// (`tm`: the stage the launch belongs to, or an untimed one)
+static int materialize_tiles(mppi_handle_t h, StageTimer& tm) {
     const unsigned grid = (unsigned)((h->d.tiles + 3) / 4);
     if (!h->limits_set) return fail(h, MPPI_E_STATE, "dim_control > 4: call mppi_set_control_limits first");
-    if (h->wide || h->cov.on) hipLaunchKernelGGL(sample_kernel<true>, dim3(grid), dim3(BLOCK), 0, s, h->core.noise, h->d, h->core.gen, (const float*)sigma_table(h));
-    else hipLaunchKernelGGL(sample_kernel<false>, dim3(grid), dim3(BLOCK), 0, s, h->core.noise, h->d, h->core.gen, (const float*)nullptr);
+    if (h->wide || h->cov.on) tm.launch(sample_kernel<true>, dim3(grid), dim3(BLOCK), 0, h->core.noise, h->d, h->core.gen, (const float*)sigma_table(h));
+    else tm.launch(sample_kernel<false>, dim3(grid), dim3(BLOCK), 0, h->core.noise, h->d, h->core.gen, (const float*)nullptr);
     HIP_TRY(h, hipGetLastError());
     h->core.tiles_valid = true;
     return MPPI_OK;
@@ -101,7 +102,8 @@ static int materialize_tiles(mppi_handle_t h, hipStream_t s) {
 // the tiles must hold the current noise for the layout/gather entry points
 int need_tiles(mppi_handle_t h, hipStream_t s) {
     if (h->core.tiles_valid) return MPPI_OK;
-    return materialize_tiles(h, s);
+    StageTimer untimed(h, -1, s);
+    return materialize_tiles(h, untimed);
 }
 
 // lambda argument of the reduce / finalize entry points -> (launch constant, device pointer or null)
@@ -135,8 +137,7 @@ int flush_state_seq(mppi_handle_t h, hipStream_t s) {
     const size_t sh1 = sizeof(float) * ((size_t)h->d.row + MPPI_MAX_DIM_STATE);
     StageTimer tm(h, 4, s);
 #define CALL_STATE_SEQ(MODEL, FASTV)                                                                  \
-    hipLaunchKernelGGL((state_seq_kernel<MODEL, FASTV>), dim3(1), dim3(WAVE), sh1, s, (const float*)h->lazy.b1, h->d.row, h->d.T, \
-                       out, h->model.ctx)
+    tm.launch(state_seq_kernel<MODEL, FASTV>, dim3(1), dim3(WAVE), sh1, (const float*)h->lazy.b1, h->d.row, h->d.T, out, h->model.ctx)
     MPPI_DISPATCH(h, CALL_STATE_SEQ);
 #undef CALL_STATE_SEQ
     HIP_TRY(h, hipGetLastError());
@@ -231,7 +232,7 @@ static int solve_fused(mppi_handle_t h, float lambda, float* action_out, float* 
         }                                                                                                                  \
         if ((int64_t)grid > (int64_t)h->fused.occ_blocks * h->cu_count) { *declined = true; break; }                       \
         StageTimer tm(h, 1, s);  /* (after the occupancy check: a declined launch leaves no empty event pair behind) */    \
-        hipLaunchKernelGGL((solve_fused_kernel<MODEL, FASTV>), dim3(grid), dim3(FUSED_BLOCK), shmem, s, A, h->d, h->core.gen, h->model.ctx, sg, fx); \
+        tm.launch(solve_fused_kernel<MODEL, FASTV>, dim3(grid), dim3(FUSED_BLOCK), shmem, A, h->d, h->core.gen, h->model.ctx, sg, fx);  \
     } while (0)
     MPPI_DISPATCH(h, CALL_FUSED);
 #undef CALL_FUSED
@@ -261,7 +262,7 @@ int mppi_sample(mppi_handle_t h, uint32_t solve_idx, void* stream) {
     h->core.tiles_valid = false;
     if (h->opt.noise_regen && !h->wide && !h->cov.on) return MPPI_OK;  // consumers regenerate eps(seed, solve, i, t, k) in registers
     StageTimer tm(h, 0, s);
-    return materialize_tiles(h, s);
+    return materialize_tiles(h, tm);
 }
 
 int mppi_inject_noise(mppi_handle_t h, const float* eps_dev, void* stream) {
@@ -308,8 +309,8 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
 #define CALL_WAVE(MODEL, FASTV)                                                                       \
         do {                                                                                          \
             const size_t shw = sizeof(float) * 4 * ((size_t)4 * h->d.R + (size_t)(h->d.T + 1) * ModelT<MODEL, FASTV>::DS); \
-            hipLaunchKernelGGL((rollout_cost_wave_kernel<MODEL, FASTV>), dim3(wgrid), dim3(BLOCK), shw, s, h->core.noise_std, \
-                               h->core.mean, h->core.x0_cur, h->core.costs, mkw, mkw_next, h->d, h->model.ctx);           \
+            tmw.launch(rollout_cost_wave_kernel<MODEL, FASTV>, dim3(wgrid), dim3(BLOCK), shw, h->core.noise_std,      \
+                       h->core.mean, h->core.x0_cur, h->core.costs, mkw, mkw_next, h->d, h->model.ctx);                 \
         } while (0)
         MPPI_DISPATCH(h, CALL_WAVE);
 #undef CALL_WAVE
@@ -333,13 +334,13 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
                                                       (size_t)h->d.row + MPPI_MAX_DIM_STATE);         \
         constexpr bool UCV = FASTV != 0;  /* the FAST kernels exist in the u_in_bounds form only (see use_fast) */ \
         if (gen)                                                                                      \
-            hipLaunchKernelGGL((rollout_cost_kernel<MODEL, FASTV, true, UCV>), dim3(grid), dim3(BLOCK), shmem, s, \
-                               h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
-                               (const float*)h->lazy.b1, ride);                                           \
+            tm.launch(rollout_cost_kernel<MODEL, FASTV, true, UCV>, dim3(grid), dim3(BLOCK), shmem,     \
+                      h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
+                      (const float*)h->lazy.b1, ride);                                                    \
         else                                                                                          \
-            hipLaunchKernelGGL((rollout_cost_kernel<MODEL, FASTV, false, UCV>), dim3(grid), dim3(BLOCK), shmem, s, \
-                               h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
-                               (const float*)h->lazy.b1, ride);                                           \
+            tm.launch(rollout_cost_kernel<MODEL, FASTV, false, UCV>, dim3(grid), dim3(BLOCK), shmem,    \
+                      h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
+                      (const float*)h->lazy.b1, ride);                                                    \
     } while (0)
     MPPI_DISPATCH(h, CALL_ROLLOUT);
 #undef CALL_ROLLOUT
@@ -377,7 +378,17 @@ int mppi_weights_reduce(mppi_handle_t h, float lambda, float* summary_out_dev, v
     const float* lam_dev = nullptr;
     if (int rc = resolve_lambda(h, lambda, &lam_dev)) return rc;
     hipStream_t s = (hipStream_t)stream;
+    // Which launches the stage makes is known up front.  The published partial rows are folded into the shard summary by
+    // summarize_kernel when sharded use needs the summary before the collective; otherwise mppi_finalize folds the rows
+    // itself when the previous solves published few of them (*live_hint, written by finalize_kernel to mapped host memory
+    // and read here without synchronising: it only steers this choice: both folds use the same summation tree, so the
+    // summary is bit-identical either way).
+    const bool many_rows = h->opt.fold_mode == 0 ? *(volatile int*)h->reduce.live_hint.host > FOLD_IN_FINALIZE_MAX_ROWS : h->opt.fold_mode == 2;
+    const bool comm = h->xchg.comm_enabled && !h->xchg.p2p_enabled;
+    // (covariance adaptation: the step between this call and mppi_finalize reads the summary)
+    const bool summarize = summary_out_dev || h->xchg.p2p_enabled || comm || !fold_fits(h) || many_rows || h->cov.on;
     StageTimer tm(h, 2, s);
+    tm.left = comm ? 0 : summarize ? 2 : 1;  // (the all-gather ends the stage: its stop event is recorded behind it)
     // one wave per tile up to reduce_blocks blocks (dense weights need the parallelism; with sparse
     // weights most waves only run the phase-A check)
     int64_t blocks = std::min<int64_t>(h->opt.reduce_blocks, (h->d.tiles + 3) / 4);
@@ -388,8 +399,8 @@ int mppi_weights_reduce(mppi_handle_t h, float lambda, float* summary_out_dev, v
     if (!gen && !h->core.tiles_valid) return fail(h, MPPI_E_STATE, "no noise: call mppi_sample or mppi_inject_noise first");
     const unsigned* mk = h->core.min_key + h->seq.min_slot;
 #define CALL_REDUCE(GPWV, GENV, WIDEV, CHAINSV, REMV)                                                 \
-    hipLaunchKernelGGL((weights_reduce_kernel<GPWV, GENV, WIDEV, CHAINSV, REMV>), grid, dim3(BLOCK), 0, s, h->core.noise, h->core.mean, h->core.costs, mk, \
-                       h->reduce.partials, h->reduce.heads, h->d, h->core.gen, lambda, lam_dev, (const float*)h->core.coltab)
+    tm.launch(weights_reduce_kernel<GPWV, GENV, WIDEV, CHAINSV, REMV>, grid, dim3(BLOCK), 0, h->core.noise, h->core.mean, h->core.costs, mk, \
+              h->reduce.partials, h->reduce.heads, h->d, h->core.gen, lambda, lam_dev, (const float*)h->core.coltab)
     // regenerated noise: four chains per basic block while a SIMD holds one or two reduction waves, two beyond (see the kernel)
     const bool chains4 = h->opt.reduce_chains == 4 || (h->opt.reduce_chains == 0 && blocks * (int64_t)h->reduce.nchunks <= 2 * (int64_t)h->cu_count);
     const bool rem = (h->d.R % 4) != 0;  // some chunk of the row leaves groups over (chunks hold 32 groups: R % 32 % 4)
@@ -402,24 +413,17 @@ int mppi_weights_reduce(mppi_handle_t h, float lambda, float* summary_out_dev, v
     else CALL_REDUCE(8, false, false, 2, false);
 #undef CALL_REDUCE
     HIP_TRY(h, hipGetLastError());
-    // Fold the published partial rows into the shard summary.  Sharded use needs the summary before the
-    // collective; otherwise mppi_finalize folds the rows itself when the previous solves published few of them
-    // (*live_hint, written by finalize_kernel to mapped host memory and read here without synchronising: it only
-    // steers this choice: both folds use the same summation tree, so the summary is bit-identical either way).
     h->reduce.summary_valid = false;
     P2pCtx p2p{};
     if (h->xchg.p2p_enabled) {  // summarize_kernel also hands the summary to every peer (and to this rank's own slot)
         next_tag(h->seq.p2p);
         p2p = p2p_ctx(h);
     }
-    const bool many_rows = h->opt.fold_mode == 0 ? *(volatile int*)h->reduce.live_hint.host > FOLD_IN_FINALIZE_MAX_ROWS : h->opt.fold_mode == 2;
-    const bool comm = h->xchg.comm_enabled && !h->xchg.p2p_enabled;
     if (comm && summary_out_dev) return fail(h, MPPI_E_INVALID, "exchange_comm: the library gathers the summaries itself (pass NULL)");
-    // (covariance adaptation: the step between this call and mppi_finalize reads the summary)
-    if (summary_out_dev || h->xchg.p2p_enabled || comm || !fold_fits(h) || many_rows || h->cov.on) {
+    if (summarize) {
         const unsigned sgrid = (unsigned)((h->reduce.colsp + SUM_COLS - 1) / SUM_COLS + 1);
-        hipLaunchKernelGGL(summarize_kernel, dim3(sgrid), dim3(SUM_BLOCK), 0, s, h->reduce.partials, h->reduce.heads, mk, (int)blocks,
-                           h->reduce.colsp, h->d.row, h->reduce.summary, comm ? h->xchg.comm_send : summary_out_dev, h->reduce.live_hint.dev, p2p);
+        tm.launch(summarize_kernel, dim3(sgrid), dim3(SUM_BLOCK), 0, h->reduce.partials, h->reduce.heads, mk, (int)blocks,
+                  h->reduce.colsp, h->d.row, h->reduce.summary, comm ? h->xchg.comm_send : summary_out_dev, h->reduce.live_hint.dev, p2p);
         HIP_TRY(h, hipGetLastError());
         h->reduce.summary_valid = true;
     }
@@ -466,7 +470,7 @@ int mppi_finalize(mppi_handle_t h, const float* summaries_dev, int num_shards, f
     {
         StageTimer tm(h, 3, s);
 #define CALL_FINALIZE(MODEL, FASTV)                                                                   \
-    hipLaunchKernelGGL((finalize_kernel<MODEL, FASTV>), dim3(1), dim3(FIN_BLOCK), shmem, s, summaries_dev, num_shards, \
+    tm.launch(finalize_kernel<MODEL, FASTV>, dim3(1), dim3(FIN_BLOCK), shmem, summaries_dev, num_shards,               \
                        h->reduce.partials, h->reduce.heads, mk, h->reduce.last_reduce_blocks, h->reduce.colsp, h->reduce.summary, h->reduce.live_hint.dev,  \
                        lambda, lam_dev, h->d.row, h->d.T, h->core.x0_cur, store_mean ? h->core.mean : (float*)nullptr, action_out,  \
                        defer ? (float*)nullptr : state_out, stats_out, h->reduce.solve_stats, sg, p2p, h->model.ctx,          \

@@ -32,11 +32,13 @@
 //   mppi_maps.hpp      map construction
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>  // hipExtLaunchKernel: a launch with events on its own dispatch (StageTimer)
 #include <rccl/rccl.h>  // types and prototypes only: the library is dlopen()ed when a communicator is asked for
 
 #include <cstddef>
 #include <cstring>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -335,10 +337,17 @@ inline int model_param_count(int model) {
            : model == MPPI_MODEL_GOALZONE ? MPPI_GP_COUNT : 0;
 }
 
-// Brackets one stage with a pair of HIP events on the caller's stream (no host synchronisation);
-// pairs accumulate until mppi_get_timing() drains them.
+// Times one stage with a pair of HIP events (no host synchronisation); pairs accumulate until mppi_get_timing() drains
+// them.  The events ride on the stage's own dispatches (hipExtLaunchKernel): the start event on its first kernel launch,
+// the stop event on its last, so a timed stage puts no marker packet on the stream and its time runs from the begin of the
+// first dispatch to the end of the last.  The stage's kernels go through launch(); an untimed stage launches them exactly
+// as hipLaunchKernelGGL does.  Two cases keep plain hipEventRecord markers: a stream that is being captured (both events,
+// around the stage), and a stage that ends in something other than a kernel of ours (`left` = 0: the stop event, behind it).
 struct StageTimer {
-    mppi_handle_t h; int stage; hipStream_t s; hipEvent_t stop = nullptr;
+    mppi_handle_t h; int stage; hipStream_t s;
+    hipEvent_t start = nullptr, stop = nullptr;  // still to be placed
+    bool ride = false;  // place them on the dispatches
+    int left = 1;       // kernel launches of the stage still to come: the stop event rides on the last of them
     static hipEvent_t next(mppi_handle_t h, int stage) {
         auto& pool = h->timers.pool[stage];
         if (h->timers.used[stage] == pool.size()) {
@@ -350,14 +359,37 @@ struct StageTimer {
         return pool[h->timers.used[stage]++].e;
     }
     StageTimer(mppi_handle_t h_, int stage_, hipStream_t s_) : h(h_), stage(stage_), s(s_) {
-        if (!h->timers.mode || (h->timers.mode == 2 && stage != 1)) return;  // timing = 2: rollout_cost stage only
-        hipEvent_t start = next(h, stage);
-        stop = start ? next(h, stage) : nullptr;
-        if (start && stop) (void)hipEventRecord(start, s);
-        else if (start) { --h->timers.used[stage]; }
+        // (stage < 0: a launch outside every stage; timing = 2: rollout_cost stage only)
+        if (stage < 0 || !h->timers.mode || (h->timers.mode == 2 && stage != 1)) return;
+        hipEvent_t e0 = next(h, stage);
+        hipEvent_t e1 = e0 ? next(h, stage) : nullptr;
+        if (!e1) { if (e0) --h->timers.used[stage]; return; }  // pool full: the stage runs untimed
+        // (what the ext launch does with events inside a capture is left alone: a captured solve keeps its markers)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        ride = hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
+        stop = e1;
+        if (ride) start = e0;
+        else (void)hipEventRecord(e0, s);
     }
     ~StageTimer() {
+        if (start) { h->timers.used[stage] -= 2; return; }  // the stage returned before its first launch: the pair goes back
         if (stop) (void)hipEventRecord(stop, s);
+    }
+    // One kernel launch of the stage: hipLaunchKernelGGL(kernel, grid, block, lds, s, a...), with the stage's events on the
+    // dispatch where they are due (flags = 0).  Errors are left to the caller's hipGetLastError().
+    template <class... F, class... A>
+    void launch(void (*kernel)(F...), dim3 grid, dim3 block, size_t lds, const A&... a) {
+        const bool last = --left == 0;
+        hipEvent_t e0 = std::exchange(start, nullptr);
+        hipEvent_t e1 = ride && last ? std::exchange(stop, nullptr) : nullptr;
+        if (!e0 && !e1) {
+            hipLaunchKernelGGL(kernel, grid, block, lds, s, a...);
+            return;
+        }
+        std::tuple<F...> formals{a...};  // (the arguments as the kernel declares them)
+        void* argv[sizeof...(F)];
+        std::apply([&](auto&... f) { size_t i = 0; ((argv[i++] = (void*)&f), ...); }, formals);
+        (void)hipExtLaunchKernel((const void*)kernel, grid, block, argv, lds, s, e0, e1, 0);
     }
 };
 
