@@ -70,8 +70,25 @@ int drain_timing(mppi_handle_t h, int stage, float* mean_ms, float* count) {
         HIP_TRY(h, hipEventElapsedTime(&ms, pool[2 * p].e, pool[2 * p + 1].e));
         sum += ms;
     }
-    if (pairs) { *mean_ms = (float)(sum / (double)pairs); *count = (float)pairs; }
     h->timers.used[stage] = 0;
+    // the rollout stage's stamp pairs (StageTimer): ticks of the wall clock, written by the kernels themselves.  They join
+    // the event pairs in the one mean; the used pairs are zeroed again (the end stamp is an atomicMax).
+    auto& t = h->timers;
+    size_t stamped = 0;
+    if (stage == 1 && t.stamps_used) {
+        std::vector<unsigned long long> st(2 * t.stamps_used);
+        HIP_TRY(h, hipDeviceSynchronize());
+        HIP_TRY(h, hipMemcpy(st.data(), t.stamps, sizeof(unsigned long long) * st.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemset(t.stamps, 0, sizeof(unsigned long long) * st.size()));
+        t.stamps_used = 0;
+        for (size_t p = 0; p < st.size(); p += 2) {
+            if (!st[p] || st[p + 1] < st[p]) continue;  // (a launch that never ran)
+            sum += (double)(st[p + 1] - st[p]) / (double)t.wall_khz;
+            ++stamped;
+        }
+    }
+    const size_t n = pairs + stamped;
+    if (n) { *mean_ms = (float)(sum / (double)n); *count = (float)n; }
     return MPPI_OK;
 }
 
@@ -177,6 +194,9 @@ int mppi_create(const MppiConfig* cfg, mppi_handle_t* out) {
     }
     if (int rc = mpo_upload(h, 1.0, 0.1, 0.2, false)) return rc;  // mppi.py:191-200
     HIP_TRY(h, hipDeviceGetAttribute(&h->cu_count, hipDeviceAttributeMultiprocessorCount, cfg->device));
+    // the rollout stage's stamp pool (StageTimer); without a wall-clock rate the stage keeps its events
+    if (hipDeviceGetAttribute(&h->timers.wall_khz, hipDeviceAttributeWallClockRate, cfg->device) != hipSuccess) h->timers.wall_khz = 0;
+    if (h->timers.wall_khz > 0) HIP_TRY(h, h->timers.stamps.alloc_set(2 * MppiSolver::Timers::STAMP_PAIRS, 0));
     HIP_TRY(h, hipDeviceSynchronize());
     return MPPI_OK;
 }
@@ -354,6 +374,7 @@ int mppi_set_option(mppi_handle_t h, const char* key, int64_t value) {
     if (k == "math") { o.math_fast = value < 0 ? 0 : value > 2 ? 2 : (int)value; return MPPI_OK; }
     if (k == "reduce_blocks") { o.reduce_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(value, 2048)); return MPPI_OK; }
     if (k == "timing") { h->timers.mode = (int)value; return MPPI_OK; }
+    if (k == "timing_source") { h->timers.source = value ? 1 : 0; return MPPI_OK; }  // 1: events for every stage (A/B of the stamps)
     if (k == "mapping") { o.mapping = value ? 1 : 0; return MPPI_OK; }
     if (k == "essps_cold") {  // the next ESSPS search (device chain and host loop) starts from the geometric grid
         h->search.essps_lo = h->search.essps_hi = 0.0;

@@ -317,7 +317,7 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
         HIP_TRY(h, hipGetLastError());
         return MPPI_OK;
     }
-    StageTimer tm(h, 1, s);
+    StageTimer tm(h, 1, s, true);  // (this stage's one kernel stamps its own time)
     const bool gen = h->opt.noise_regen && !h->core.injected && !h->cov.on;
     if (!gen && !h->core.tiles_valid) return fail(h, MPPI_E_STATE, "no noise: call mppi_sample or mppi_inject_noise first");
     h->seq.min_slot ^= 1;
@@ -328,6 +328,7 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
     float* ride = h->lazy.pending_out;
     if (ride) { if (int rc = order_behind_pending(h, s)) return rc; }
     const unsigned grid = (unsigned)((h->d.tiles + 3) / 4) + (ride ? 1u : 0u);
+    unsigned long long* stamps = tm.take_stamps();
 #define CALL_ROLLOUT(MODEL, FASTV)                                                                    \
     do {                                                                                              \
         const size_t shmem = sizeof(float) * std::max((size_t)8 * h->d.R + (size_t)h->d.T * ModelT<MODEL, FASTV>::KROW, \
@@ -336,11 +337,11 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
         if (gen)                                                                                      \
             tm.launch(rollout_cost_kernel<MODEL, FASTV, true, UCV>, dim3(grid), dim3(BLOCK), shmem,     \
                       h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
-                      (const float*)h->lazy.b1, ride);                                                    \
+                      (const float*)h->lazy.b1, ride, stamps);                                                   \
         else                                                                                          \
             tm.launch(rollout_cost_kernel<MODEL, FASTV, false, UCV>, dim3(grid), dim3(BLOCK), shmem,    \
                       h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
-                      (const float*)h->lazy.b1, ride);                                                    \
+                      (const float*)h->lazy.b1, ride, stamps);                                                   \
     } while (0)
     MPPI_DISPATCH(h, CALL_ROLLOUT);
 #undef CALL_ROLLOUT

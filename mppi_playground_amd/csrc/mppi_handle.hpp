@@ -298,10 +298,17 @@ struct MppiSolver {
     } ring;
 
     // per-stage event pairs (option "timing"; stage 4 = the deferred state sequence): start0, stop0, start1, stop1, ...
+    // The rollout stage (1) is stamped by rollout_cost_kernel itself where it can be (StageTimer): `stamps` is its pool of
+    // {start, end} pairs of 100 MHz wall-clock ticks, zeroed when the handle is created and again by every drain.
     struct Timers {
+        static constexpr size_t STAMP_PAIRS = 8192;  // as deep as the event pool
         int mode = 0;                  // 0 off, 1 every stage, 2 the rollout stage only
+        int source = 0;                // "timing_source": 0 = stamps where they apply, 1 = events everywhere
         std::vector<Event> pool[5];
         size_t used[5] = {0, 0, 0, 0, 0};
+        DevBuf<unsigned long long> stamps;  // [STAMP_PAIRS][2]
+        size_t stamps_used = 0;        // pairs handed to launches since the last drain
+        int wall_khz = 0;              // hipDeviceAttributeWallClockRate (0: unknown, nothing is stamped)
     } timers;
 };
 
@@ -343,10 +350,21 @@ inline int model_param_count(int model) {
 // first dispatch to the end of the last.  The stage's kernels go through launch(); an untimed stage launches them exactly
 // as hipLaunchKernelGGL does.  Two cases keep plain hipEventRecord markers: a stream that is being captured (both events,
 // around the stage), and a stage that ends in something other than a kernel of ours (`left` = 0: the stop event, behind it).
+//
+// A STAMPED stage carries no events at all.  A dispatch with profiling events costs the solve about 4.5 us more than one
+// without (profiles/r09_timing_markers.md), so the one launch of the rollout stage, rollout_cost_kernel, reads the 100 MHz
+// wall clock itself: `stampable` stages take a pair of the handle's stamp pool (take_stamps(), handed to the kernel as an
+// argument) and launch exactly as an untimed stage does.  What a stamped stage time IS: from the first instruction of block
+// 0 (dispatched first) to the last instruction of the block that finishes last, (end - start) / wall-clock rate.  It lies
+// INSIDE the dispatch — it leaves out what the packet processor does before the first and after the last wave — and so reads
+// a little below the dispatch-bound event time and the rocprofv3 kernel time (profiles/r10_rollout_stamps.md has the
+// difference).  Stamps need an uncaptured stream, a known wall-clock rate and "timing_source" = 0; a full stamp pool leaves
+// the stage untimed, like a full event pool.  Every other stage and kernel keeps its events.
 struct StageTimer {
     mppi_handle_t h; int stage; hipStream_t s;
     hipEvent_t start = nullptr, stop = nullptr;  // still to be placed
     bool ride = false;  // place them on the dispatches
+    bool stamped = false;  // no events: the stage's kernel writes a stamp pair
     int left = 1;       // kernel launches of the stage still to come: the stop event rides on the last of them
     static hipEvent_t next(mppi_handle_t h, int stage) {
         auto& pool = h->timers.pool[stage];
@@ -358,15 +376,17 @@ struct StageTimer {
         }
         return pool[h->timers.used[stage]++].e;
     }
-    StageTimer(mppi_handle_t h_, int stage_, hipStream_t s_) : h(h_), stage(stage_), s(s_) {
+    StageTimer(mppi_handle_t h_, int stage_, hipStream_t s_, bool stampable = false) : h(h_), stage(stage_), s(s_) {
         // (stage < 0: a launch outside every stage; timing = 2: rollout_cost stage only)
         if (stage < 0 || !h->timers.mode || (h->timers.mode == 2 && stage != 1)) return;
+        // (what the ext launch does with events inside a capture is left alone: a captured solve keeps its markers)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        const bool eager = hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
+        if (stampable && eager && !h->timers.source && h->timers.wall_khz > 0 && h->timers.stamps) { stamped = true; return; }
         hipEvent_t e0 = next(h, stage);
         hipEvent_t e1 = e0 ? next(h, stage) : nullptr;
         if (!e1) { if (e0) --h->timers.used[stage]; return; }  // pool full: the stage runs untimed
-        // (what the ext launch does with events inside a capture is left alone: a captured solve keeps its markers)
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        ride = hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
+        ride = eager;
         stop = e1;
         if (ride) start = e0;
         else (void)hipEventRecord(e0, s);
@@ -374,6 +394,12 @@ struct StageTimer {
     ~StageTimer() {
         if (start) { h->timers.used[stage] -= 2; return; }  // the stage returned before its first launch: the pair goes back
         if (stop) (void)hipEventRecord(stop, s);
+    }
+    // The stamp pair of a stamped stage's launch, taken right before it (null: untimed, or timed with events)
+    unsigned long long* take_stamps() {
+        auto& t = h->timers;
+        if (!stamped || t.stamps_used == MppiSolver::Timers::STAMP_PAIRS) return nullptr;
+        return t.stamps.p + 2 * t.stamps_used++;
     }
     // One kernel launch of the stage: hipLaunchKernelGGL(kernel, grid, block, lds, s, a...), with the stage's events on the
     // dispatch where they are due (flags = 0).  Errors are left to the caller's hipGetLastError().

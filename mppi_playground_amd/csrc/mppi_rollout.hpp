@@ -176,9 +176,20 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void rollout_cost_kernel(c
                                                              float* __restrict__ mean_used,
                                                              float* __restrict__ x0_used, Dims d, GenCtx gen,
                                                              ModelCtx ctx, const float* __restrict__ b1_in,
-                                                             float* __restrict__ b1_state_out) {
+                                                             float* __restrict__ b1_state_out,
+                                                             unsigned long long* __restrict__ stamps) {
     using M = ModelT<MODEL, FAST>;
     __shared__ float s_min[BLOCK / WAVE];
+    // `stamps` (or null: untimed) is the launch's pair of 100 MHz wall-clock stamps {start, end} (StageTimer): block 0, which
+    // is dispatched first, stores the start; every block raises the end as its last act.  end - start runs from block 0's
+    // first instruction to the last block's last one: the stage's time as seen from inside the dispatch.
+    // The pointer waits for the end of the block in LDS, not in a pair of SGPRs held across the horizon loop: six more live
+    // SGPRs took the kernel from eight waves per SIMD to seven.
+    __shared__ unsigned long long* s_stamps;
+    if (threadIdx.x == 0) {
+        s_stamps = stamps;
+        if (stamps != nullptr && blockIdx.x == 0) stamps[0] = wall_clock64();
+    }
     // [4*R] mean groups, [4*R] zeros (samples that do not inherit the mean), then [T*KROW] step rows
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     // One extra block (the last) when the PREVIOUS solve left its state sequence pending (option "lazy_state_seq"): the
@@ -188,6 +199,7 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void rollout_cost_kernel(c
         for (int i = threadIdx.x; i < d.row + M::DS; i += BLOCK) s_dyn[i] = b1_in[i];
         __syncthreads();
         batch1_rollout<MODEL, FAST>(ctx, s_dyn + d.row, s_dyn, d.T, b1_state_out);
+        if (stamps != nullptr && threadIdx.x == 0) (void)atomicMax(stamps + 1, (unsigned long long)wall_clock64());
         return;
     }
 #ifdef MPPI_AB_VGPR_FLOOR  // (A/B knob of scripts/build_variant.sh: same code at the occupancy of an 85-VGPR build)
@@ -232,6 +244,8 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void rollout_cost_kernel(c
 #pragma unroll
         for (int w = 1; w < BLOCK / WAVE; ++w) m = fminf(m, s_min[w]);
         if (m < INFINITY) atomicMin(min_key, float_to_key(m));
+        unsigned long long* const st = s_stamps;
+        if (st != nullptr) (void)atomicMax(st + 1, (unsigned long long)wall_clock64());
     }
 }
 
