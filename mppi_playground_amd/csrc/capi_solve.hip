@@ -350,6 +350,14 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
     return MPPI_OK;
 }
 
+#ifdef MPPI_ROLLOUT_TRACE
+// (experiments only) the [4 * blocks][6] device buffer that the next rollout launches stamp their timeline into; null: none
+extern "C" int mppi_debug_rollout_trace(void* rows_dev) {
+    unsigned long long* p = (unsigned long long*)rows_dev;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_rollout_trace), &p, sizeof(p)) == hipSuccess ? MPPI_OK : MPPI_E_HIP;
+}
+#endif
+
 int mppi_get_costs(mppi_handle_t h, float* dst, int on_device, void* stream) {
     if (!h || !dst) return fail(h, MPPI_E_INVALID, "null");
     return copy_small(h, dst, h->core.costs, sizeof(float) * (size_t)h->d.N, on_device != 0, true, (hipStream_t)stream);

@@ -5,6 +5,45 @@
 
 namespace mppi {
 
+// -DMPPI_ROLLOUT_TRACE (experiments only: scripts/rollout_timeline.py): lane 0 of every wave of rollout_cost_kernel stores the
+// 100 MHz clock at its entry (0), behind the prologue's barrier (1), at the entry and the exit of the horizon loop (2) and
+// at the end of its block (4), and where it ran (5: HW_REG_HW_ID, HW_REG_XCC_ID << 32), into row `tile` of a [tiles][6] buffer
+// that mppi_debug_rollout_trace() hands in.  The loop's two stamps are one store behind the loop, the low words of the clock
+// in column 2 (entry | exit << 32; column 3 stays 0): the entry's word waits in ONE scalar register (a store in front of the
+// loop, or a register pair across it, costs the racing kernel a wave per SIMD).
+// Off in the product: no code, no symbol.
+#ifdef MPPI_ROLLOUT_TRACE
+static __device__ unsigned long long* g_rollout_trace;
+__device__ __forceinline__ void rollout_trace(int k) {
+    unsigned long long* const rows = *(unsigned long long* volatile*)&g_rollout_trace;  // (read again at every stamp: not held across the loop)
+    if (rows == nullptr || (threadIdx.x & 63) != 0) return;
+    unsigned long long v = (unsigned long long)wall_clock64();
+    if (k == 5)  // s_getreg_b32 hwreg(id, 0, 32): id | (32 - 1) << 11; HW_ID = 4, XCC_ID = 20
+        v = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) |
+            (unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32;
+    rows[((size_t)blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6)) * 6 + k] = v;
+}
+__device__ __forceinline__ void rollout_trace_loop(unsigned entry_lo) {
+    unsigned long long* const rows = *(unsigned long long* volatile*)&g_rollout_trace;
+    if (rows == nullptr) return;  // (every lane stores the same word to a wave-uniform address: no divergent branch, two data VGPRs)
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    rows[((size_t)blockIdx.x * (BLOCK / WAVE) + wid) * 6 + 2] = (unsigned long long)(unsigned)wall_clock64() << 32 | entry_lo;
+}
+#define ROLLOUT_TRACE(k) rollout_trace(k)
+#define ROLLOUT_TRACE_LOOP_ENTRY() const unsigned trace_entry_lo = (unsigned)wall_clock64()
+#define ROLLOUT_TRACE_LOOP_EXIT() rollout_trace_loop(trace_entry_lo)
+#else
+#define ROLLOUT_TRACE(k) do { } while (0)
+#define ROLLOUT_TRACE_LOOP_ENTRY() do { } while (0)
+#define ROLLOUT_TRACE_LOOP_EXIT() do { } while (0)
+#endif
+
+#ifdef MPPI_AB_NO_DRAIN_PRIO  // (A/B knob of scripts/build_variant.sh: the same code, every wave at priority 0 throughout)
+#define MPPI_DRAIN_PRIO(p) __builtin_amdgcn_s_setprio(0)
+#else
+#define MPPI_DRAIN_PRIO(p) __builtin_amdgcn_s_setprio(p)
+#endif
+
 // ------------------------------------------------------------------------------------------
 // Steps 1b-3 fused: U = clamp(mean + eps), rollout, stage + terminal cost (mppi.py:266-336).
 // Reads the noise once (16 B per lane per 4/dc steps), writes costs[N] and the shard minimum.
@@ -84,17 +123,33 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
     // groups that lie completely inside the horizon: SPG steps each, no per-step bound checks
     const int full = d.T / SPG;
     if (GEN) {
-        for (int r = 0; r < full; ++r) {
-            const int rn = min(r + 1, d.R - 1);
-            const float4 en = noise_group<GEN>(np, rn, gi, gen, d, &pins);  // independent chain, interleaved with the steps
-            const float4 m4n = mean4[rn];
-            const float ev[4] = {e.x, e.y, e.z, e.w};
-            const float mv[4] = {m4.x, m4.y, m4.z, m4.w};
+        // Even drain: VALU issue goes by priority, then age, so the waves of a SIMD would finish in age order and the
+        // youngest walk the end of their horizons alone.  A wave in the first half of its groups outranks one in the
+        // second half: the waves of a SIMD converge.  s_setprio takes an immediate, hence two copies of the loop (the
+        // outer loop is unrolled).  Three copies keep the one loop: the library math (a second loop takes the goal zone's redo
+        // from 80 to 82 VGPRs, a wave per SIMD), racing math = 1 (64 -> 65 VGPRs, a wave per SIMD) and the X0OUT copy, whose
+        // `t == 0` test would stay inside the second loop.
+        constexpr bool DRAIN = FAST != 0 && !X0OUT && !(MODEL == MPPI_MODEL_RACING && FAST == 1);
+        ROLLOUT_TRACE_LOOP_ENTRY();
+        int r = 0;
 #pragma unroll
-            for (int g = 0; g < SPG; ++g) one_step(ev + g * DC, mv + g * DC);
-            e = en;
-            m4 = m4n;
+        for (int half = DRAIN ? 0 : 1; half < 2; ++half) {
+            if (DRAIN && half == 0) MPPI_DRAIN_PRIO(1);
+            if (DRAIN && half == 1) MPPI_DRAIN_PRIO(0);
+            const int end = half == 0 ? full >> 1 : full;
+            for (; r < end; ++r) {
+                const int rn = min(r + 1, d.R - 1);
+                const float4 en = noise_group<GEN>(np, rn, gi, gen, d, &pins);  // independent chain, interleaved with the steps
+                const float4 m4n = mean4[rn];
+                const float ev[4] = {e.x, e.y, e.z, e.w};
+                const float mv[4] = {m4.x, m4.y, m4.z, m4.w};
+#pragma unroll
+                for (int g = 0; g < SPG; ++g) one_step(ev + g * DC, mv + g * DC);
+                e = en;
+                m4 = m4n;
+            }
         }
+        ROLLOUT_TRACE_LOOP_EXIT();
     } else {
         // Tiles: loads return in order (one vmcnt), so the first map gather consumed after a noise load also
         // waits for that load.  Keep two groups in flight and issue the load of group r+2 at the very END of
@@ -184,10 +239,17 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void rollout_cost_kernel(c
     // is dispatched first, stores the start; every block raises the end as its last act.  end - start runs from block 0's
     // first instruction to the last block's last one: the stage's time as seen from inside the dispatch.
     // The pointer waits for the end of the block in LDS, not in a pair of SGPRs held across the horizon loop: six more live
-    // SGPRs took the kernel from eight waves per SIMD to seven.
+    // SGPRs took the kernel from eight waves per SIMD to seven.  `costs` and `min_key` wait there too: the loop's second
+    // bound (trajectory_cost, "Even drain") needs the registers (racing: 103 SGPRs and seven waves per SIMD without, 99 with).
+    ROLLOUT_TRACE(0);
+    ROLLOUT_TRACE(5);
     __shared__ unsigned long long* s_stamps;
+    __shared__ float* s_costs;
+    __shared__ unsigned* s_min_key;
     if (threadIdx.x == 0) {
         s_stamps = stamps;
+        s_costs = costs;
+        s_min_key = min_key;
         if (stamps != nullptr && blockIdx.x == 0) stamps[0] = wall_clock64();
     }
     // [4*R] mean groups, [4*R] zeros (samples that do not inherit the mean), then [T*KROW] step rows
@@ -219,6 +281,7 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void rollout_cost_kernel(c
     }
     for (int f = threadIdx.x; f < d.T * M::KROW; f += BLOCK) s_ktab[f] = ctx.ref[f];
     __syncthreads();
+    ROLLOUT_TRACE(1);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int64_t tile = (int64_t)blockIdx.x * (BLOCK / WAVE) + wid;
     // the minimum key is double-buffered: this launch accumulates into `min_key` (reset by the
@@ -233,17 +296,18 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void rollout_cost_kernel(c
         bool bad = false;
         const float4* mp = inherit ? s_mean4 : s_mean4 + d.R;
         total = lane_cost<MODEL, FAST, GEN, UC>(np, gi, gen, mp, s_ktab, x0, d, ctx);
-        if (i < d.N) costs[i] = total;
+        if (i < d.N) s_costs[i] = total;
         else total = INFINITY;
     }
     const float wm = wave_min(total);
     if (lane == 0) s_min[wid] = wm;
     __syncthreads();
+    ROLLOUT_TRACE(4);
     if (threadIdx.x == 0) {
         float m = s_min[0];
 #pragma unroll
         for (int w = 1; w < BLOCK / WAVE; ++w) m = fminf(m, s_min[w]);
-        if (m < INFINITY) atomicMin(min_key, float_to_key(m));
+        if (m < INFINITY) atomicMin(s_min_key, float_to_key(m));
         unsigned long long* const st = s_stamps;
         if (st != nullptr) (void)atomicMax(st + 1, (unsigned long long)wall_clock64());
     }

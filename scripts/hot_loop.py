@@ -7,7 +7,9 @@ launch-uniform variant (mppi_rollout.hpp: lane_cost): a start outside the positi
 single-block loop (a general-wheel-base copy); --copy unit_L is the loop without the division by the wheel base: of the
 copies that carry the full step (as many transcendentals as the longest), the one whose FMAs negate a single scalar
 register — the map's cell size of Markstein's division, r = fma(-cell, q0, p) — where the general copies also negate the
-wheel base, fma(-L, q0, vt).  It stops with an error unless exactly one copy qualifies.  --copy all lists every copy."""
+wheel base, fma(-L, q0, vt).  The horizon is walked in two halves at two wave priorities (trajectory_cost, "Even drain"),
+one copy of the loop each: both are reported, and it stops with an error unless there are one or two of them with the same
+VALU and transcendental counts.  --copy all lists every copy."""
 import collections
 import re
 import sys
@@ -69,10 +71,12 @@ def main():
     elif copy == "unit_L":
         full = [x for x in all_loops if census(x[1])[1] == census(longest[1])[1]]
         unit = [x for x in full if len(negated_sgprs(x[1])) == 1]
-        if len(unit) != 1:
-            sys.exit(f"--copy unit_L: {len(unit)} full-step copies negate a single SGPR in their FMAs (expected 1): "
-                     + ", ".join(f"{lab} {sorted(negated_sgprs(lp))}" for lab, lp in full))
-        label, loop = unit[0]
+        if len(unit) not in (1, 2) or len({census(lp)[1:3] for _, lp in unit}) != 1:
+            sys.exit(f"--copy unit_L: {len(unit)} full-step copies negate a single SGPR in their FMAs (expected 1, or the 2 "
+                     "halves of the horizon with one VALU count): " + ", ".join(f"{lab} {sorted(negated_sgprs(lp))}" for lab, lp in full))
+        for label, loop in unit[:-1]:
+            report(label, loop)
+        label, loop = unit[-1]
     else:
         sys.exit(f"unknown --copy {copy}")
     report(label, loop)
