@@ -323,6 +323,11 @@ int mppi_get_state_seq_timing(mppi_handle_t h, float* out2_host);
  * are NaN (the `stats_out` of that call: the stale plan is visible in the solve it happened in), the flag below is
  * raised and the handle stays on the multi-kernel path until mppi_set_option("fused_rearm", 1).  It never hangs. */
 int mppi_fused_error(mppi_handle_t h);
+/* Which geometry the last mppi_solve took: the grid and the trajectories per block (a multiple of 64, <= 512) of the single
+ * launch, or 0 / 0 if that solve ran as separate kernels (option "fused_solve" = 0, a problem the single launch does not take,
+ * a launch configuration declined by the occupancy check, or a handle demoted by mppi_fused_error).  Host bookkeeping only:
+ * no synchronisation. */
+int mppi_fused_geometry(mppi_handle_t h, int* blocks_out, int* spb_out);
 /* Step 7 inside mppi_finalize (mppi.py:423-443,598-620): Savitzky-Golay smoothing of [history(T-1); a(T)] per control
  * dimension (symmetric-flip padding, valid cross-correlation, keep the last T), applied whenever mppi_finalize is
  * called with store_mean != 0; the smoothed sequence is what is returned, stored as the warm start and rolled out,

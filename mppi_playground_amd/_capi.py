@@ -34,7 +34,7 @@ SYMBOLS = [
     "mppi_p2p_alloc", "mppi_p2p_connect", "mppi_p2p_exchange", "mppi_p2p_error", "mppi_rollout_actions", "mppi_rollout_samples", "mppi_top_samples", "mppi_top_candidates", "mppi_rollout_candidates", "mppi_set_option", "mppi_get_timing",
     "mppi_set_center_path", "mppi_ref_window", "mppi_set_path_index", "mppi_get_path_index", "mppi_get_reference",
     "mppi_model_step", "mppi_comm_unique_id", "mppi_comm_init", "mppi_comm_exchange", "mppi_comm_destroy",
-    "mppi_set_auto_lambda", "mppi_lbps_lambda_device", "mppi_lbps_brent_device", "mppi_search_error", "mppi_clone_state", "mppi_mpo_set_state", "mppi_mpo_step_device", "mppi_fused_error",
+    "mppi_set_auto_lambda", "mppi_lbps_lambda_device", "mppi_lbps_brent_device", "mppi_search_error", "mppi_clone_state", "mppi_mpo_set_state", "mppi_mpo_step_device", "mppi_fused_error", "mppi_fused_geometry",
     "mppi_search_passes", "mppi_grid_lookup", "mppi_mpo_log_temperature_ptr", "mppi_join_state_seq", "mppi_state_seq_serial", "mppi_get_state_seq_timing", "mppi_comm_info",
     "mppi_set_covariance_adaptation", "mppi_update_covariance", "mppi_get_sigma_table", "mppi_set_sigma_table",
 ]
@@ -105,6 +105,7 @@ def load():
     lib.mppi_mpo_set_state.argtypes = [vp, vp]
     lib.mppi_mpo_step_device.argtypes = [vp, vp]
     lib.mppi_fused_error.argtypes = [vp]
+    lib.mppi_fused_geometry.argtypes = [vp, vp, vp]
     lib.mppi_search_passes.argtypes = [vp, vp]
     lib.mppi_comm_info.argtypes = [vp, vp, vp]
     lib.mppi_join_state_seq.argtypes = [vp, u32, vp]

@@ -172,6 +172,14 @@ extern "C" int mppi_debug_fused_trace(mppi_handle_t h, int* out10) {  // (out: 5
 #endif
 int mppi_fused_error(mppi_handle_t h) { return h ? h->fused.error.get() : 0; }
 
+// grid and trajectories per block of the last mppi_solve if it ran as the single launch; 0 / 0 if it took the multi-kernel path
+int mppi_fused_geometry(mppi_handle_t h, int* blocks_out, int* spb_out) {
+    if (!h) return MPPI_E_INVALID;
+    if (blocks_out) *blocks_out = h->fused.last_blocks;
+    if (spb_out) *spb_out = h->fused.last_spb;
+    return MPPI_OK;
+}
+
 // 1 if a poll of the exchange buffer ever timed out on this handle (read without synchronising)
 int mppi_p2p_error(mppi_handle_t h) { return h ? h->xchg.p2p_error.get() : 0; }
 

@@ -207,8 +207,8 @@ static int solve_fused(mppi_handle_t h, float lambda, float* action_out, float* 
     A.stats_keep = h->reduce.solve_stats; A.summary_out = h->reduce.summary;
     const SgFilter sg{h->reduce.sg_coeffs, h->reduce.sg_history, h->reduce.sg_window};
     const FusedCtx fx{h->fused.cells, h->fused.error.dev, h->seq.fused, h->opt.fused_timeout_ticks};
-    // G = min(#CUs, ceil(N / 64)) blocks, each owning spb (a multiple of 64, <= 1024) consecutive trajectories: ONE wave
-    // of rollouts per block as long as there are CUs left (the rest of its 1024 threads share the block's reductions and
+    // G = min(#CUs, ceil(N / 64)) blocks, each owning spb (a multiple of 64, <= 512) consecutive trajectories: ONE wave
+    // of rollouts per block as long as there are CUs left (the rest of its 512 threads share the block's reductions and
     // the regeneration of its weighted noise rows, which a block of 256 trajectories spends ~5 us on)
     const int64_t gmax = std::min(FUSED_MAX_BLOCKS, h->cu_count);
     unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(gmax, (h->d.N + 63) / 64));
@@ -217,6 +217,7 @@ static int solve_fused(mppi_handle_t h, float lambda, float* action_out, float* 
     if (h->d.N <= FUSED_AUTO_MAX_SAMPLES) grid = std::min<unsigned>(grid, (unsigned)FUSED_SMALL_BLOCKS);
     A.spb = (int)(((h->d.N + grid - 1) / grid + 63) / 64 * 64);
     grid = (unsigned)((h->d.N + A.spb - 1) / A.spb);  // (no block without trajectories)
+    h->fused.last_blocks = (int)grid; h->fused.last_spb = A.spb;  // (mppi_fused_geometry; cleared by mppi_solve if the launch is declined)
 #define CALL_FUSED(MODEL, FASTV)                                                                      \
     do {                                                                                              \
         const size_t shmem = sizeof(float) * ((size_t)8 * h->d.R + (size_t)h->d.T * ModelT<MODEL, FASTV>::KROW + 2 * (size_t)h->d.row + \
@@ -541,6 +542,7 @@ int mppi_solve(mppi_handle_t h, const float* x0_dev, uint32_t solve_idx, float l
             return MPPI_OK;
         }
     }
+    h->fused.last_blocks = h->fused.last_spb = 0;  // this solve is the multi-kernel path (mppi_fused_geometry)
     if (int rc = mppi_rollout_cost(h, stream)) return rc;
     if (dev && h->search.auto_rule == MPPI_AUTO_ESSPS) {
         if (int rc = mppi_essps_lambda_device(h, h->search.auto_param, h->search.auto_lo, h->search.auto_hi, stream)) return rc;

@@ -33,8 +33,8 @@ namespace mppi {
 //   itself (same inputs, same order: the same temperature in every block).
 // Costs and the minimum are BIT-IDENTICAL to the multi-kernel path (same device functions); the statistics and the
 // weighted row are summed over another partition, i.e. the temperature and the action agree to rounding.  Deterministic.
-// A poll that does not complete within ~2 s (a block that never became resident: the device is shared with another
-// cooperative kernel) raises *error, voids the outputs and returns — no hang.
+// A poll that does not complete within its budget (FUSED_TIMEOUT_TICKS below: 20 ms by default; a block that never became
+// resident: the device is shared with another cooperative kernel) raises *error, voids the outputs and returns — no hang.
 // 512 threads, not 1024: at 1024 the kernel is capped at 128 VGPRs, spilled to scratch memory, and every wave executed
 // the double-precision invariants the compiler hoisted out of the rounds loop for the scalar step (7 us per round on a
 // 28 us solve; profiles/r03_experiments.md) — hence also fused_scalar_step as a non-inlined function.
@@ -42,7 +42,10 @@ constexpr int FUSED_BLOCK = 512;
 constexpr int FUSED_MAX_BLOCKS = 256;
 constexpr int FUSED_MAX_ROW = 128;
 constexpr int FUSED_SMALL_BLOCKS = 32;       // up to this many blocks no hop is spent on the global minimum or on a broadcast
-constexpr int FX_CELLS = FUSED_MAX_ROW + 8;  // per (phase, block): >= 4 + row, >= 97
+constexpr int FX_CELLS = FUSED_MAX_ROW + 8;  // per (phase, block): >= 4 + row, >= 98 (96 statistics sums + the block's reference and maximum)
+static_assert(FUSED_MAX_ROW + MPPI_SUMMARY_HEAD <= FX_CELLS, "a block's row cells: the summary head and the widest row");
+static_assert(STATS_L * 3 + 2 <= FX_CELLS, "a block's statistics cells: 3 sums per temperature, its reference cost and its maximum");
+static_assert(FUSED_MAX_BLOCKS <= FUSED_BLOCK / 2, "the min / max gather: thread b reads block b's minimum, thread FUSED_BLOCK / 2 + b its maximum");
 enum { FX_MIN = 0, FX_STATS = 1 /* +2*round */, FX_BCAST = 2 /* +2*round */, FX_ROW = 7, FX_PHASES = 8 };
 enum { FUSED_RULE_NONE = 0, FUSED_RULE_ESSPS = 1, FUSED_RULE_LBPS = 2 };
 // A poll that cannot complete within `timeout_ticks` gives up (100 MHz wall clock; default 20 ms — three orders of magnitude
@@ -203,15 +206,19 @@ __global__ __launch_bounds__(FUSED_BLOCK) void solve_fused_kernel(FusedArgs A, D
     constexpr int NWV = FUSED_BLOCK / WAVE;
     constexpr bool UC = FAST != 0;
     constexpr int KG = 32;                         // cells a thread keeps in flight: every gather is ONE round trip (G <= 256)
-    constexpr int KS = (FUSED_SMALL_BLOCKS + FUSED_BLOCK / FX_CELLS - 1) / (FUSED_BLOCK / FX_CELLS);                          // ... with few blocks (G <= 32 over >= 7 thread groups)
+    constexpr int KS = (FUSED_SMALL_BLOCKS + FUSED_BLOCK / FX_CELLS - 1) / (FUSED_BLOCK / FX_CELLS);  // 11: ... with few blocks (G <= 32 over the 3 row groups of the row fold)
     constexpr int COLS = STATS_L * 3;              // 96 statistics columns
-    constexpr int SPARTS = FUSED_BLOCK / COLS;     // 10 row groups of the statistics combine
+    constexpr int SPARTS = FUSED_BLOCK / COLS;     // 5 row groups of the statistics combine
     constexpr int CW = FX_CELLS;                   // column slots of the row fold (>= 4 + row)
-    constexpr int RPARTS = FUSED_BLOCK / CW;       // 7 row groups of the row fold
+    constexpr int RPARTS = FUSED_BLOCK / CW;       // 3 row groups of the row fold
+    static_assert(KS * RPARTS >= FUSED_SMALL_BLOCKS, "row fold with few blocks: KS cells per thread over RPARTS row groups reach every block");
+    static_assert(KS * SPARTS >= FUSED_SMALL_BLOCKS, "statistics combine with few blocks: KS cells per thread over SPARTS row groups reach every block");
+    static_assert(NWV * STATS_L * 3 >= FUSED_BLOCK && 2 * 2048 >= 4 * FUSED_BLOCK && SPARTS * COLS <= 2048,
+                  "the slice fold is staged in s_p ([Q][W] = FUSED_BLOCK floats) and s_scratch ([nsl][4 RP] = 4 FUSED_BLOCK floats)");
     __shared__ float s_c[FUSED_BLOCK];             // this block's costs (padded), later its weights
     __shared__ float s_p[NWV][STATS_L][3];
     __shared__ float s_w[NWV][4];                  // per-wave scalars
-    __shared__ double s_scratch[2048];             // statistics combine [SPARTS][COLS] doubles; aliased: row partials, 4096 floats
+    __shared__ double s_scratch[2048];             // statistics combine [SPARTS][COLS] doubles; aliased: row partials, 2048 of its 4096 floats
     __shared__ float s_fold[RPARTS][CW];           // block 0's row fold
     __shared__ FusedSearchLds s_search;
     double* const s_sumd = s_search.sumd; double* const s_vald = s_search.vald;
@@ -445,7 +452,7 @@ __global__ __launch_bounds__(FUSED_BLOCK) void solve_fused_kernel(FusedArgs A, D
         int RP = 1;
         while (RP < d.R) RP <<= 1;  // float4 groups per row, rounded up to a power of two (<= 32)
         const int r = tid & (RP - 1), slice = tid / RP, nsl = FUSED_BLOCK / RP;
-        float* s_part = reinterpret_cast<float*>(s_scratch);  // [nsl][4 * RP] = 4096 floats
+        float* s_part = reinterpret_cast<float*>(s_scratch);  // [nsl][4 * RP] = 4 * FUSED_BLOCK = 2048 floats
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         if (bse != 0.0f && r < d.R) {
             for (int sidx = slice; sidx < A.spb; sidx += nsl) {
@@ -467,9 +474,9 @@ __global__ __launch_bounds__(FUSED_BLOCK) void solve_fused_kernel(FusedArgs A, D
 #pragma unroll
         for (int j = 0; j < 4; ++j) s_part[slice * 4 * RP + 4 * r + j] = acc[j];
         __syncthreads();
-        {   // fold the slices in two steps (fixed order): W = 4 RP columns x Q = 1024 / W groups of nsl / Q = 4 slices each
+        {   // fold the slices in two steps (fixed order): W = 4 RP columns x Q = 512 / W groups of nsl / Q = 4 slices each
             const int W = 4 * RP, Q = FUSED_BLOCK / W, c = tid & (W - 1), q = tid / W;
-            float* s_half = &s_p[0][0][0];  // [Q][W] = 1024 floats (the statistics' staging is free by now)
+            float* s_half = &s_p[0][0][0];  // [Q][W] = 512 of its 768 floats (the statistics' staging is free by now)
             float v = 0.0f;
             for (int sl = q; sl < nsl; sl += Q) v += s_part[sl * W + c];
             s_half[q * W + c] = v;

@@ -233,6 +233,7 @@ struct MppiSolver {
         double grid0_lo = 0.0, grid0_hi = 0.0;
         uint64_t occ_key = 0;          // (math level, LDS bytes) the cached occupancy below belongs to
         int occ_blocks = 0;            // resident blocks of solve_fused_kernel per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor)
+        int last_blocks = 0, last_spb = 0;  // grid and trajectories per block of the last mppi_solve if it was the single launch, else 0 (mppi_fused_geometry)
     } fused;
 
     // queries after a solve (capi_topk.hip)

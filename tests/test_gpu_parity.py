@@ -2870,7 +2870,7 @@ def test_uneven_shards_match_the_unsharded_solver():
     ("pendulum", 50, 1000, "ESSPS", {}), ("pendulum", 15, 256, "LBPS", {}), ("pendulum", 15, 1000, "MPO", {}),
     ("racing", 25, 4000, 1.0, {}), ("racing", 50, 5000, 300.0, dict(exploration=0.2, use_sg_filter=True)),
     ("nav2d", 50, 65536, "ESSPS", {}), ("nav2d", 30, 3000, "LBPS", dict(use_sg_filter=True, sg_window_size=7, sg_poly_order=2)),
-    ("cartpole", 64, 262144, "ESSPS", dict(use_sg_filter=True)), ("mountaincar", 100, 1025, 0.1, {}),
+    ("cartpole", 64, 131072, "ESSPS", dict(use_sg_filter=True)), ("mountaincar", 100, 1025, 0.1, {}),
     ("goalzone", 30, 3000, 1.0, {}), ("mjcartpole", 50, 1000, 1.0, {}), ("cartpole", 10, 100, 0.001, {})])
 def test_single_launch_solve_equals_the_multi_kernel_path(model, T, N, lam, kw):
     """mppi_solve as ONE cooperative kernel (solve_fused_kernel, the default whenever the problem is resident at once)
@@ -2907,6 +2907,11 @@ def test_single_launch_solve_equals_the_multi_kernel_path(model, T, N, lam, kw):
         a1, s1 = fused.forward(state)
         a2, s2 = multi.forward(state)
         assert not fused._h.lib.mppi_fused_error(fused._h.h)
+        blocks, spb = C.c_int(0), C.c_int(0)
+        fused._h.call("mppi_fused_geometry", C.byref(blocks), C.byref(spb))
+        assert blocks.value > 0 and spb.value > 0, "the solver under test took the multi-kernel path"
+        multi._h.call("mppi_fused_geometry", C.byref(blocks), C.byref(spb))
+        assert (blocks.value, spb.value) == (0, 0)
         # the rollout is the same arithmetic; the sums behind the temperature and the action run over another partition
         assert torch.equal(fused._costs, multi._costs)
         assert fused.last_stats()["cmin"] == multi.last_stats()["cmin"]
