@@ -120,12 +120,28 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
         for (int j = 0; j < DS; ++j) s[j] = sn[j];
         ++t;
     };
-    // groups that lie completely inside the horizon: SPG steps each, no per-step bound checks
-    const int full = d.T / SPG;
+    // Groups walked by the loops below: SPG steps each, no per-step bound checks.  Tiles: every group that lies completely
+    // inside the horizon, d.T / SPG.  Regenerating loop: only the groups that still have a SUCCESSOR to generate,
+    // (d.T - 1) / SPG.  An iteration of that loop generates the noise of the next group, a whole Philox4x32-10 and two
+    // Box-Muller pairs; when T*dc is a multiple of 4 the last complete group is also the last group (d.T / SPG == d.R), the
+    // clamped look-ahead would generate it a second time and nothing would read the result.  That group's steps go through
+    // the ragged epilogue below instead, which consumes `e` and `m4` and generates nothing: the same operations per step
+    // in the same order, the same order of the cost sum, R generations for R groups.  When T*dc is no multiple of 4 the
+    // two bounds are equal.
+    // Per model: the fast-math functors are compiled with FP contraction `fast` (mppi_models.hpp), and which product of a
+    // sum becomes the FMA is the compiler's choice per copy of the step.  The move keeps every bit only where the loop's
+    // and the epilogue's copies are contracted alike: held bit for bit against the tile loop for racing, nav2d and the
+    // pendulum (tests/test_gpu_rollout_last_group.py).  The cart-pole's are not (stage cost a*a + 0.1*w*w + 0.1*x*x: a*a
+    // is the bare product in the loop, 0.1*w*w in the epilogue; 6 % of the costs changed at T = 4 and 8), so it and the models
+    // nobody has compared keep the loop over every complete group.
+    constexpr bool LAST_GROUP_IN_EPILOGUE =
+        GEN && (MODEL == MPPI_MODEL_RACING || MODEL == MPPI_MODEL_NAV2D || MODEL == MPPI_MODEL_PENDULUM);
+    const int full = LAST_GROUP_IN_EPILOGUE ? (d.T - 1) / SPG : d.T / SPG;
     if (GEN) {
         // Even drain: VALU issue goes by priority, then age, so the waves of a SIMD would finish in age order and the
-        // youngest walk the end of their horizons alone.  A wave in the first half of its groups outranks one in the
-        // second half: the waves of a SIMD converge.  s_setprio takes an immediate, hence two copies of the loop (the
+        // youngest walk the end of their horizons alone.  A wave in the first half of the loop's groups (`full` of them: the
+        // last group of the horizon is the epilogue's, and runs at the second half's priority) outranks one in the second
+        // half: the waves of a SIMD converge.  s_setprio takes an immediate, hence two copies of the loop (the
         // outer loop is unrolled).  Three copies keep the one loop: the library math (a second loop takes the goal zone's redo
         // from 80 to 82 VGPRs, a wave per SIMD), racing math = 1 (64 -> 65 VGPRs, a wave per SIMD) and the X0OUT copy, whose
         // `t == 0` test would stay inside the second loop.
@@ -168,7 +184,7 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
             e1 = *nptr;
         }
     }
-    if (t < d.T) {  // ragged last group (T*dc not a multiple of 4)
+    if (t < d.T) {  // last group: ragged (T*dc not a multiple of 4), or, behind the regenerating loop, the complete last one
         const float ev[4] = {e.x, e.y, e.z, e.w};
         const float mv[4] = {m4.x, m4.y, m4.z, m4.w};
 #pragma unroll
