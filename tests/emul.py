@@ -68,8 +68,11 @@ def search_lib():
         _search.search_lbps_grid.argtypes = [vp, i, d, d, d, vp]
         _search.search_fminbound_poly.argtypes = [d, d, d, d, d, vp, vp]
         _search.search_essps.argtypes = [vp, i, d, d, d, d, vp, vp]
+        _search.search_essps_grid.argtypes = [vp, i, d, d, d, d, vp, vp]
         _search.search_essps_first_grid.argtypes = [d, d, d, vp]
         _search.search_mpo.argtypes = [vp, i, i, d, d, d, vp]
+        _search.search_lbps_grid_step.argtypes = [vp, vp, i, vp, vp, vp]
+        _search.search_mpo_step_stats.argtypes = [vp, d, d, vp, vp]
     return _search
 
 
@@ -87,16 +90,28 @@ def lbps_grid(costs, delta, lo, hi):
     return out.value
 
 
+def lbps_grid_step(grid, obj, last):
+    """One lbps_grid_step<32> on objectives formed by the caller -> (lo, hi, lam)."""
+    g, o = np.ascontiguousarray(grid, np.float64), np.ascontiguousarray(obj, np.float64)
+    assert g.shape == (32,) and o.shape == (32,)
+    lo, hi, lam = C.c_double(0), C.c_double(0), C.c_double(0)
+    assert search_lib().search_lbps_grid_step(_p(g), _p(o), int(bool(last)), C.byref(lo), C.byref(hi), C.byref(lam)) == 0
+    return lo.value, hi.value, lam.value
+
+
 def fminbound_poly(a, b, c, lo, hi):
     out, nf = C.c_double(0), C.c_int(0)
     assert search_lib().search_fminbound_poly(a, b, c, lo, hi, C.byref(out), C.byref(nf)) == 0
     return out.value, nf.value
 
 
-def essps(costs, target, lo, hi, lam_prev=0.0, with_passes=False):
+def essps(costs, target, lo, hi, lam_prev=0.0, with_passes=False, grid_argument=False):
+    """grid_argument: the exponent as the 32-temperature pass of the device's ESSPS chain forms it, (cmin - c) * (1 / lam),
+    instead of mppi_softmax_stats's (-c) / lam - (-cmin) / lam."""
     c = np.ascontiguousarray(costs, np.float32)
     out, passes = C.c_double(0), C.c_int(0)
-    assert search_lib().search_essps(_p(c), len(c), target, lo, hi, lam_prev, C.byref(out), C.byref(passes)) == 0
+    fn = search_lib().search_essps_grid if grid_argument else search_lib().search_essps
+    assert fn(_p(c), len(c), target, lo, hi, lam_prev, C.byref(out), C.byref(passes)) == 0
     return (out.value, passes.value) if with_passes else out.value
 
 
@@ -111,3 +126,12 @@ def mpo(cost_rows, lam0=1.0, epsilon=0.1, lr=0.2):
     out = np.zeros(c.shape[0], np.float64)
     assert search_lib().search_mpo(_p(c), c.shape[1], c.shape[0], lam0, epsilon, lr, _p(out)) == 0
     return out
+
+
+def mpo_step_stats(state4, epsilon, lr, stats5):
+    """One mpo_step from the statistics {cmin, cmax, se, se2, sec} -> (new {log T, m, v, t}, lambda)."""
+    s, st = np.array(state4, np.float64), np.ascontiguousarray(stats5, np.float64)
+    assert s.shape == (4,) and st.shape == (5,)
+    lam = C.c_double(0)
+    assert search_lib().search_mpo_step_stats(_p(s), epsilon, lr, _p(st), C.byref(lam)) == 0
+    return s, lam.value

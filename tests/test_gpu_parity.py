@@ -26,6 +26,7 @@ import torch
 import parity_report
 from helpers import (CASES, MODEL_CFG, SOLVER_KW, Band, band_closed_loop, band_fixed, band_rule, band_rule_lambda, load, oracle_problem, orc,
                      rel_err, same_lbps_minimum, sg_coeffs)
+from stats_cases import brent_cost_vector, essps_cost_shapes
 
 pytestmark = pytest.mark.gpu
 
@@ -997,28 +998,6 @@ def test_baseline_configs_against_oracle(model, T, N, lam):
     check_rel("state_seq_vs_oracle_rollout", s.cpu().numpy()[0], P.rollout_single(x0, a.cpu().numpy()), TOL)
 
 
-def brent_cost_vector(rng, N, kind):
-    """Cost vectors for the LBPS search: the shapes of the shipped models' costs and awkward ones."""
-    if kind == 0:    # nav2d-like: distances + collision penalties
-        c = rng.uniform(10, 40, N) + 1e4 * rng.integers(0, 30, N) * (rng.random(N) < 0.5)
-    elif kind == 1:  # racing-like
-        c = rng.uniform(300, 3000, N) + 1e4 * rng.integers(0, 25, N) * (rng.random(N) < 0.4)
-    elif kind == 2:  # pendulum / cartpole-like: a smooth, narrow range
-        c = rng.gamma(2.0, rng.uniform(0.5, 50.0), N) + rng.uniform(0, 100)
-    elif kind == 3:  # a range of e^40
-        c = np.exp(rng.uniform(-20, 20, N))
-    elif kind == 4:  # mixed signs, any scale
-        c = rng.standard_normal(N) * 10.0 ** rng.integers(-3, 6)
-    elif kind == 5:  # all equal: the objective has no range term
-        c = np.full(N, float(rng.uniform(-5, 5)))
-    elif kind == 6:  # few distinct values
-        c = rng.integers(0, max(2, N // 50), N).astype(np.float64)
-    else:            # one clear winner
-        c = rng.uniform(100, 200, N)
-        c[int(rng.integers(0, N))] = 1.0
-    return np.ascontiguousarray(c, dtype=np.float32)
-
-
 def brent_both(solver, costs, delta=0.01, lo=0.01, hi=10.0):
     """(host loop's temperature, device search's temperature, probes of either) on the same uploaded cost vector."""
     st = solver._stream()
@@ -1033,7 +1012,8 @@ def brent_both(solver, costs, delta=0.01, lo=0.01, hi=10.0):
     return lam_host.value, lam_dev.value, solver._h.lib.mppi_search_passes(solver._h.h, st)
 
 
-@pytest.mark.parametrize("N", [1, 63, 256, 257, 1000, 4096, 65536, 65537, 262144, 1048576, 3000001])
+@pytest.mark.parametrize("N", [1, 63, 256, 257, 1000, 4096, 16384, 16385, 32769, 49153, 65536, 65537, 262144, 1048576,
+                               2097152, 2097153, 3000001])
 def test_device_brent_equals_the_host_loop_to_the_bit(N):
     """LBPS's bounded Brent search as ONE kernel (mppi_lbps_brent_device, the default of lambda_="LBPS") against the same
     search as a host loop over mppi_softmax_stats (mppi_lbps_lambda; csrc/host_search.hpp::fminbound on both sides): the
@@ -2521,16 +2501,7 @@ def test_essps_device_search_equals_the_host_loop_on_random_costs():
     solver.forward(torch.tensor([1.0, 0.0]))  # (a handle with costs[N] allocated and a noise identity)
     h, st = solver._h, solver._stream()
     N = 300_000
-    shapes = {
-        "gauss": lambda: rng.standard_normal(N) * 3.0 + 50.0,
-        "gauss_small_spread": lambda: rng.standard_normal(N) * 0.02 + 7.0,
-        "exponential": lambda: rng.exponential(5.0, N),
-        "lognormal": lambda: np.exp(rng.standard_normal(N) * 1.5),
-        "two_clusters": lambda: np.where(rng.random(N) < 0.05, rng.standard_normal(N) * 0.5, 40.0 + rng.standard_normal(N)),
-        "offset_1e6": lambda: 1.0e6 + rng.standard_normal(N) * 4.0,
-        "all_equal": lambda: np.full(N, 3.25),
-        "one_outlier": lambda: np.concatenate([[-1.0e4], 100.0 + rng.standard_normal(N - 1)]),
-    }
+    shapes = essps_cost_shapes(rng, N)
     for name, draw in shapes.items():
         c = draw().astype(np.float32)
         cd = torch.from_numpy(c).cuda()
