@@ -101,7 +101,7 @@ typedef struct MppiConfig {
 const char* mppi_version(void);
 /* Integer version of THIS header's function signatures; bindings compare it with the constant they were written
  * against and refuse a stale library (a changed argument list would otherwise be called with shifted arguments). */
-#define MPPI_ABI_VERSION 11
+#define MPPI_ABI_VERSION 12
 int mppi_abi_version(void);
 /* Number of visible HIP devices (0 => the product cannot run; callers must fail loudly). */
 int mppi_device_count(void);
@@ -288,6 +288,34 @@ int mppi_set_covariance_adaptation(mppi_handle_t h, int enable, float rate, floa
 int mppi_update_covariance(mppi_handle_t h, float lambda /* > 0, or MPPI_LAMBDA_DEVICE */, void* stream);
 int mppi_get_sigma_table(mppi_handle_t h, float* table_out, int on_device, void* stream);
 int mppi_set_sigma_table(mppi_handle_t h, const float* table, int on_device, void* stream);
+/* The control-cost term — the `action_costs` the reference fills on every solve at mppi.py:294-316 and leaves out of the
+ * cost sum at :330-336 (the KL term of the MPPI objective).  Opt-in; off, nothing changes and nothing else is launched.
+ * For sample i of a solve that samples around the warm start mean[T][dc] (fp32, one rounding per operation, no FMA):
+ *     inv[t][k] = 0 for t = 0 (the reference fills rows 1..T-1 only), 1 / (s[t][k] * s[t][k]) for t >= 1
+ *                 (s: `sigmas`, or the per-step sigma table while the covariance adaptation is on)
+ *     g[t][k]   = mean[t][k] * inv[t][k]
+ *     A_i       = sum over t = 0..T-1, k = 0..dc-1, in this order, of g[t][k] * U_i[t][k]
+ *     cost_i    = c0_i + kappa * A_i,  kappa = weight * lambda
+ * U_i is the solver-clamped perturbed action; `mean` is the real warm start for EVERY sample, the exploration samples
+ * (which do not inherit it when sampling) included (mppi.py:313); c0_i is the stage + terminal cost.  Everything after
+ * the rollout (minimum, temperature rules, weights, queries, mppi_get_costs) sees cost_i.
+ *   mppi_set_action_cost  on / off with weight >= 0 (1 = the reference's sketch; the paper scales the term by 1 - alpha).
+ *                         Needs every sigma > 0.  Leaves everything else alone; allowed between solves.  While on:
+ *                         native models roll out with the term inside rollout_cost (instantiations of their own),
+ *                         mppi_solve takes the multi-kernel sequence (mppi_fused_geometry reports 0 / 0) and option
+ *                         "mapping" = 1 returns MPPI_E_INVALID.  Copied by mppi_clone_state.
+ *   mppi_set_action_cost_lambda  the lambda of the term for mppi_rollout_cost, which has no lambda argument: a value >= 0
+ *                         (0: the term is zero), or MPPI_LAMBDA_DEVICE — the temperature in the handle's device memory
+ *                         WHEN THE ROLLOUT STARTS (the previous solve's ESSPS / LBPS result, the MPO dual's current
+ *                         temperature); kappa = 0 while no device-resident rule has left one.  Stays until set again.
+ *                         mppi_solve sets it from its own lambda argument on every call.
+ *   mppi_add_action_cost  costs[i] += weight * lambda * A_i as a pass of its own over the noise tiles (materialised first if
+ *                         need be) around the CURRENT mean, then the minimum key is refreshed as by mppi_set_costs.  The
+ *                         generic path's way to the term (after mppi_set_costs, before mppi_weights_reduce; any
+ *                         dim_control); on a native handle a second, independent evaluation: same bits as the rollout's. */
+int mppi_set_action_cost(mppi_handle_t h, int enable, float weight);
+int mppi_set_action_cost_lambda(mppi_handle_t h, float lambda /* >= 0, or MPPI_LAMBDA_DEVICE */);
+int mppi_add_action_cost(mppi_handle_t h, float lambda /* >= 0, or MPPI_LAMBDA_DEVICE */, void* stream);
 /* Lazily completed state sequences (mppi_set_option("lazy_state_seq", 1)).  The reference returns `state_seq` — the batch-1
  * rollout of the solution, mppi.py:448-449,508-524 — with the action sequence, but nothing on a control loop's critical
  * path needs it: the next solve samples around the mean, env.step applies a[0].  With the option set, mppi_finalize /

@@ -272,6 +272,7 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
         CLONE(cov.lim);
     }
     dst->cov.on = src->cov.on; dst->cov.rate = src->cov.rate; dst->cov.floor = src->cov.floor; dst->cov.ready = false;
+    dst->ac = src->ac;  // the control-cost term: switch, weight and the temperature of the next stand-alone rollout
     CLONE(core.mean);
     CLONE(core.mean_used);
     CLONE(reduce.solve_stats);
@@ -375,6 +376,7 @@ int mppi_set_option(mppi_handle_t h, const char* key, int64_t value) {
     if (k == "reduce_blocks") { o.reduce_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(value, 2048)); return MPPI_OK; }
     if (k == "timing") { h->timers.mode = (int)value; return MPPI_OK; }
     if (k == "timing_source") { h->timers.source = value ? 1 : 0; return MPPI_OK; }  // 1: events for every stage (A/B of the stamps)
+    if (k == "mapping" && value && h->ac.on) return fail(h, MPPI_E_INVALID, "the control-cost term is not available with mapping = 1");
     if (k == "mapping") { o.mapping = value ? 1 : 0; return MPPI_OK; }
     if (k == "essps_cold") {  // the next ESSPS search (device chain and host loop) starts from the geometric grid
         h->search.essps_lo = h->search.essps_hi = 0.0;

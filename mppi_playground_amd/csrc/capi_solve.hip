@@ -1,6 +1,8 @@
 // capi_solve.hip — C ABI (include/mppi_hip.h): the solve — noise, rollout + costs, weights + reduction, finalize, the lazily
 // completed state sequence, the single-launch solve and mppi_solve, which chains them.  The whole hot path is this one unit
 // (only the device-resident temperature searches live in capi_search.hip).
+#include <cmath>
+
 #include "mppi_handle.hpp"
 #include "mppi_layout.hpp"
 
@@ -118,6 +120,18 @@ int resolve_lambda(mppi_handle_t h, float lambda, const float** lam_dev) {
     return MPPI_OK;
 }
 
+// Launch arguments of the control-cost term for `lambda` (> 0, MPPI_LAMBDA_DEVICE, or anything else: no temperature).  A
+// device-resident rule that has not left a temperature yet gives the term a zero factor (the warm start of a first solve
+// is zero anyway; the reference would multiply by the rule's name there).
+static ActionCostArgs action_cost_args(mppi_handle_t h, float lambda) {
+    ActionCostArgs a{};
+    a.sigtab = (h->wide || h->cov.on) ? sigma_table(h) : nullptr;
+    a.weight = h->ac.weight;
+    if (lambda == MPPI_LAMBDA_DEVICE) a.lambda_dev = h->search.lambda_dev_valid ? h->search.lambda_dev.p : nullptr;
+    else if (lambda > 0.0f) a.lambda = lambda;
+    return a;
+}
+
 // A pending state sequence is about to be completed on `s`: if that is not the stream its finalize_kernel ran on, order `s`
 // behind everything enqueued there so far (an event recorded NOW on the producing stream sits after finalize's write of b1).
 static int order_behind_pending(mppi_handle_t h, hipStream_t s) {
@@ -150,6 +164,7 @@ static constexpr int64_t FUSED_AUTO_MAX_SAMPLES = 4096;          // fixed temper
 static constexpr int64_t FUSED_AUTO_MAX_SAMPLES_SEARCH = 16384;  // ESSPS / LBPS on the device
 static bool fused_applies(mppi_handle_t h, float lambda) {
     if (!h->opt.fused_mode || h->cfg.model == MPPI_MODEL_GENERIC || h->opt.mapping != 0) return false;
+    if (h->ac.on) return false;  // the control-cost term lives in the multi-kernel rollout only (like the covariance adaptation)
     // measured (profiles/r03_experiments.md, r03_visitD_fused_crossover.txt): a cell round trip costs about as much as a
     // kernel boundary, so the single launch wins where it replaces more kernel boundaries than it needs round trips — with
     // a fixed temperature up to a few thousand samples (27 vs 32 us for racing at N = 1024, 29 vs 32 at 4096, 33 vs 32 at
@@ -292,6 +307,7 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
     if (!h) return MPPI_E_INVALID;
     if (int rc = check_ready(h)) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (h->ac.on && h->opt.mapping == 1) return fail(h, MPPI_E_INVALID, "the control-cost term is not available with mapping = 1");
     if (h->opt.mapping == 1) {  // comparison variant: one wavefront per trajectory, reference-layout noise
         if (int rc = flush_state_seq(h, s)) return rc;
         if (!h->core.noise_std) HIP_TRY(h, h->core.noise_std.alloc((size_t)h->d.N * h->d.row));
@@ -330,12 +346,22 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
     if (ride) { if (int rc = order_behind_pending(h, s)) return rc; }
     const unsigned grid = (unsigned)((h->d.tiles + 3) / 4) + (ride ? 1u : 0u);
     unsigned long long* stamps = tm.take_stamps();
+    const bool term = h->ac.on;  // the control-cost term: its own instantiations, 4R more floats of LDS for g
+    const ActionCostArgs aca = action_cost_args(h, h->ac.lambda);
 #define CALL_ROLLOUT(MODEL, FASTV)                                                                    \
     do {                                                                                              \
-        const size_t shmem = sizeof(float) * std::max((size_t)8 * h->d.R + (size_t)h->d.T * ModelT<MODEL, FASTV>::KROW, \
+        const size_t shmem = sizeof(float) * std::max((size_t)(term ? 12 : 8) * h->d.R + (size_t)h->d.T * ModelT<MODEL, FASTV>::KROW, \
                                                       (size_t)h->d.row + MPPI_MAX_DIM_STATE);         \
         constexpr bool UCV = FASTV != 0;  /* the FAST kernels exist in the u_in_bounds form only (see use_fast) */ \
-        if (gen)                                                                                      \
+        if (term && gen)                                                                              \
+            tm.launch(rollout_action_cost_kernel<MODEL, FASTV, true, UCV>, dim3(grid), dim3(BLOCK), shmem,     \
+                      h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
+                      (const float*)h->lazy.b1, ride, stamps, aca);                                              \
+        else if (term)                                                                                \
+            tm.launch(rollout_action_cost_kernel<MODEL, FASTV, false, UCV>, dim3(grid), dim3(BLOCK), shmem,    \
+                      h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
+                      (const float*)h->lazy.b1, ride, stamps, aca);                                              \
+        else if (gen)                                                                                 \
             tm.launch(rollout_cost_kernel<MODEL, FASTV, true, UCV>, dim3(grid), dim3(BLOCK), shmem,     \
                       h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
                       (const float*)h->lazy.b1, ride, stamps);                                                   \
@@ -376,6 +402,80 @@ int mppi_set_costs(mppi_handle_t h, const float* src, int on_device, void* strea
     if (!h || !src) return fail(h, MPPI_E_INVALID, "null");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = copy_small(h, h->core.costs, src, sizeof(float) * (size_t)h->d.N, true, on_device != 0, s)) return rc;
+    HIP_TRY(h, hipMemsetAsync(h->core.min_key + h->seq.min_slot, 0xFF, sizeof(unsigned), s));
+    const unsigned grid = (unsigned)std::min<int64_t>((h->d.N + BLOCK - 1) / BLOCK, 1024);
+    hipLaunchKernelGGL(min_cost_kernel, dim3(grid), dim3(BLOCK), 0, s, h->core.costs, h->d.N, h->core.min_key + h->seq.min_slot);
+    HIP_TRY(h, hipGetLastError());
+    return MPPI_OK;
+}
+
+// costs[i] += kappa * A_i from the noise tiles: the control-cost term as a pass of its own (mppi_add_action_cost).  One
+// lane per sample, the groups of its row in order — the same operations in the same order as the rollout kernel's lanes.
+__global__ __launch_bounds__(BLOCK) void action_cost_kernel(const float4* __restrict__ noise, const float* __restrict__ mean,
+                                                            float* __restrict__ costs, Dims d,
+                                                            const float* __restrict__ coltab /* wide rows, else null */,
+                                                            ActionCostArgs ac) {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= d.N) return;
+    const int64_t tile = i >> 6;
+    const int lane = (int)(i & 63);
+    const bool inherit = (d.sample_offset + i) < d.inherit_count;
+    const int dc = d.dc;
+    float A = 0.0f;
+    for (int r = 0; r < d.R; ++r) {
+        const float4 e4 = noise[(tile * d.R + r) * 64 + lane];
+        const float ev[4] = {e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int f = 4 * r + j;
+            if (f >= d.row) break;
+            const int k = f % dc;
+            const float m = mean[f];
+            const float sg = ac.sigtab ? ac.sigtab[f] : d.sigma[k];
+            float lo, hi;
+            if (coltab) { lo = coltab[4 * d.R + f]; hi = coltab[8 * d.R + f]; }
+            else { lo = d.u_min[k]; hi = d.u_max[k]; }
+            const float g = action_cost_g(m, action_cost_inv(f / dc, sg));
+            const float u = clampf((inherit ? m : 0.0f) + ev[j], lo, hi);
+            A = action_cost_accumulate(A, g, u);
+        }
+    }
+    const float kappa = action_cost_kappa(ac.weight, ac.lambda_dev ? *ac.lambda_dev : ac.lambda);
+    costs[i] = action_cost_total(costs[i], kappa, A);
+}
+
+int mppi_set_action_cost(mppi_handle_t h, int enable, float weight) {
+    if (!h) return MPPI_E_INVALID;
+    if (!(weight >= 0.0f) || !std::isfinite(weight)) return fail(h, MPPI_E_INVALID, "control-cost term: the weight must be finite and >= 0");
+    if (enable && h->opt.mapping == 1) return fail(h, MPPI_E_INVALID, "the control-cost term is not available with mapping = 1");
+    if (enable)
+        for (int k = 0; k < std::min(h->dc, (int)MPPI_MAX_DIM_CONTROL); ++k)
+            if (!(h->d.sigma[k] > 0.0f)) return fail(h, MPPI_E_INVALID, "control-cost term: every sigma must be > 0");
+    if (int rc = settle_state_seq(h)) return rc;  // (a pending state sequence rides in the rollout launch of ITS setting)
+    h->ac.on = enable != 0;
+    h->ac.weight = weight;
+    return MPPI_OK;
+}
+
+int mppi_set_action_cost_lambda(mppi_handle_t h, float lambda) {
+    if (!h) return MPPI_E_INVALID;
+    if (lambda != MPPI_LAMBDA_DEVICE && (!(lambda >= 0.0f) || !std::isfinite(lambda)))
+        return fail(h, MPPI_E_INVALID, "control-cost term: lambda must be >= 0 or MPPI_LAMBDA_DEVICE");
+    h->ac.lambda = lambda;
+    return MPPI_OK;
+}
+
+int mppi_add_action_cost(mppi_handle_t h, float lambda, void* stream) {
+    if (!h) return MPPI_E_INVALID;
+    if (lambda != MPPI_LAMBDA_DEVICE && (!(lambda >= 0.0f) || !std::isfinite(lambda)))
+        return fail(h, MPPI_E_INVALID, "control-cost term: lambda must be >= 0 or MPPI_LAMBDA_DEVICE");
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = need_tiles(h, s)) return rc;
+    const unsigned agrid = (unsigned)((h->d.N + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(action_cost_kernel, dim3(agrid), dim3(BLOCK), 0, s, h->core.noise, h->core.mean, h->core.costs, h->d,
+                       h->wide ? (const float*)h->core.coltab : (const float*)nullptr, action_cost_args(h, lambda));
+    HIP_TRY(h, hipGetLastError());
+    // the minimum key, the way mppi_set_costs refreshes it
     HIP_TRY(h, hipMemsetAsync(h->core.min_key + h->seq.min_slot, 0xFF, sizeof(unsigned), s));
     const unsigned grid = (unsigned)std::min<int64_t>((h->d.N + BLOCK - 1) / BLOCK, 1024);
     hipLaunchKernelGGL(min_cost_kernel, dim3(grid), dim3(BLOCK), 0, s, h->core.costs, h->d.N, h->core.min_key + h->seq.min_slot);
@@ -532,6 +632,7 @@ int mppi_solve(mppi_handle_t h, const float* x0_dev, uint32_t solve_idx, float l
     if (dev && h->search.auto_rule == MPPI_AUTO_NONE)
         return fail(h, MPPI_E_STATE, "MPPI_LAMBDA_DEVICE: no temperature rule configured (mppi_set_auto_lambda)");
     if (x0_dev) h->core.x0_cur = x0_dev;  // (mppi_bind_state)
+    if (h->ac.on) h->ac.lambda = lambda;  // the term's temperature is this solve's argument (mppi_set_action_cost_lambda)
     if (int rc = mppi_sample(h, solve_idx, stream)) return rc;
     if (fused_applies(h, lambda)) {
         if (int rc = flush_state_seq(h, (hipStream_t)stream)) return rc;  // (pending from an earlier multi-kernel solve)

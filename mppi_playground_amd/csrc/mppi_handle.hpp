@@ -199,6 +199,13 @@ struct MppiSolver {
         bool ready = false;            // mppi_weights_reduce ran and mppi_finalize has not yet: the step may run
     } cov;
 
+    // the control-cost term (mppi.py:294-316,330-336; mppi_set_action_cost): cost_i += weight * lambda * A_i
+    struct ActionCost {
+        bool on = false;
+        float weight = 1.0f;
+        float lambda = 0.0f;           // what mppi_rollout_cost multiplies by: > 0, MPPI_LAMBDA_DEVICE, or 0 (none yet)
+    } ac;
+
     // temperature: statistics passes, the device-resident ESSPS / LBPS / Brent / MPO searches
     struct Search {
         DevBuf<float> stats_part;      // [STATS_BLOCKS][max(4, STATS_L*3)]

@@ -1,6 +1,7 @@
 // mppi_rollout.hpp — Steps 1b-3 (mppi.py:266-336): clamp, N x T rollout and stage / terminal costs — rollout_cost_kernel (lane per trajectory) and the literal wavefront-per-trajectory variant.
 // Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
+#include "mppi_action_cost.hpp"
 #include "mppi_sample.hpp"
 
 namespace mppi {
@@ -60,11 +61,16 @@ __device__ __forceinline__ void rollout_trace_loop(unsigned entry_lo) {
 // VAR: a launch-uniform model variant the kernel has branched on OUTSIDE the horizon loop (racing: unit wheel base).
 // X0OUT (models with EntryGeneral only): the start lies outside the model's position clamp — launch-uniform, x0 is the
 // same for every lane — so the stage cost of step 0 takes the bounds-tested map lookup (every later state is clamped).
-template <int MODEL, int FAST, bool GEN, bool UC, bool VAR = false, bool X0OUT = false>
+// AC: the opt-in control-cost term (mppi.py:294-316,330-336; mppi_action_cost.hpp).  `g4` is the block's LDS copy of
+// g = mean * inv_covariance in the grouping of `mean4` — the REAL mean for every lane, exploration lanes included
+// (mppi.py:313) — read one group at a time where its steps run (no look-ahead: four VGPRs instead of eight); the lane
+// accumulates A = sum g * U over its solver-clamped actions and adds kappa * A behind the cost sum.  `kappa` waits in LDS
+// (see rollout_cost_kernel on what SGPRs held across the loop cost).  Off: no code, `g4` and `kappa` are null.
+template <int MODEL, int FAST, bool GEN, bool UC, bool VAR = false, bool X0OUT = false, bool AC = false>
 __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, uint64_t gi, const GenCtx& gen,
                                                  const float4* mean4, const float* ktab,
                                                  const float* __restrict__ x0, const Dims& d, const ModelCtx& ctx_in,
-                                                 bool& bad) {
+                                                 bool& bad, const float4* g4 = nullptr, const float* kappa = nullptr) {
     using M = ModelT<MODEL, FAST>;
     using K = typename M::K;
     constexpr int DS = M::DS, DC = M::DC, SPG = 4 / DC;
@@ -103,12 +109,17 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
         for (int k = 0; k < DC; ++k) pu[k] = pl[k] = clampf(m0[k] + e0[k], lo[k], hi[k]);
     }
     int t = 0;
-    auto one_step = [&](const float* ev, const float* mv) {
+    float A = 0.0f;  // (AC) sum over (t, k) of g * U, sequential fp32
+    auto one_step = [&](const float* ev, const float* mv, const float* gv) {
         const K kcur = knext;
         knext = M::load_k(ktab, min(t + 1, d.T - 1));
         float u[DC];
 #pragma unroll
         for (int k = 0; k < DC; ++k) u[k] = clampf(mv[k] + ev[k], lo[k], hi[k]);
+        if constexpr (AC) {
+#pragma unroll
+            for (int k = 0; k < DC; ++k) A = action_cost_accumulate(A, gv[k], u[k]);
+        }
         float sn[DS], ss[DS];
         if constexpr (MODEL == MPPI_MODEL_RACING) M::step(ctx, s, u, sn, ss, bad, UC, FAST != 0, VAR);
         else M::step(ctx, s, u, sn, ss, bad, UC, FAST != 0);
@@ -159,8 +170,10 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
                 const float4 m4n = mean4[rn];
                 const float ev[4] = {e.x, e.y, e.z, e.w};
                 const float mv[4] = {m4.x, m4.y, m4.z, m4.w};
+                float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if constexpr (AC) { const float4 gq = g4[r]; gv[0] = gq.x; gv[1] = gq.y; gv[2] = gq.z; gv[3] = gq.w; }
 #pragma unroll
-                for (int g = 0; g < SPG; ++g) one_step(ev + g * DC, mv + g * DC);
+                for (int g = 0; g < SPG; ++g) one_step(ev + g * DC, mv + g * DC, gv + g * DC);
                 e = en;
                 m4 = m4n;
             }
@@ -175,8 +188,10 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
             const float4 m4n = mean4[min(r + 1, d.R - 1)];
             const float ev[4] = {e.x, e.y, e.z, e.w};
             const float mv[4] = {m4.x, m4.y, m4.z, m4.w};
+            float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if constexpr (AC) { const float4 gq = g4[r]; gv[0] = gq.x; gv[1] = gq.y; gv[2] = gq.z; gv[3] = gq.w; }
 #pragma unroll
-            for (int g = 0; g < SPG; ++g) one_step(ev + g * DC, mv + g * DC);
+            for (int g = 0; g < SPG; ++g) one_step(ev + g * DC, mv + g * DC, gv + g * DC);
             e = e1;
             m4 = m4n;
             const float4* nptr = np + (int64_t)min(r + 2, d.R - 1) * 64;
@@ -187,9 +202,14 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
     if (t < d.T) {  // last group: ragged (T*dc not a multiple of 4), or, behind the regenerating loop, the complete last one
         const float ev[4] = {e.x, e.y, e.z, e.w};
         const float mv[4] = {m4.x, m4.y, m4.z, m4.w};
+        float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (AC) {  // (t is a multiple of SPG here and t < T: group t / SPG < R)
+            const float4 gq = g4[t / SPG];
+            gv[0] = gq.x; gv[1] = gq.y; gv[2] = gq.z; gv[3] = gq.w;
+        }
 #pragma unroll
         for (int g = 0; g < SPG; ++g)
-            if (t < d.T) one_step(ev + g * DC, mv + g * DC);
+            if (t < d.T) one_step(ev + g * DC, mv + g * DC, gv + g * DC);
     }
     // terminal cost: zero action, stale prev_action U[:, max(T-2,0)] and stale t = T-1
     // (mppi.py:318-328); knext already holds the constants of row T-1
@@ -197,7 +217,8 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
 #pragma unroll
     for (int k = 0; k < DC; ++k) zero[k] = 0.0f;
     const float term = M::cost(ctx, knext, s, zero, pl, bad);
-    return acc.total(term);
+    if constexpr (AC) return action_cost_total(acc.total(term), *kappa, A);
+    else return acc.total(term);
 }
 
 // Total cost of one lane's trajectory: picks the launch-uniform copy of the horizon loop (racing: unit wheel base; a start
@@ -205,26 +226,27 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
 // mountain car, goal zone) — redoes a lane that left one with the library math.  Racing and nav2d take any finite start
 // (EntryGeneral) and carry no redo: inlining the library-math walk next to the hot loop cost the racing kernel 18 VGPRs,
 // two waves per SIMD and 3.6 % of its time (profiles/r04_experiments.md).
-template <int MODEL, int FAST, bool GEN, bool UC>
+// AC: every copy carries the control-cost term (the redo computes its own A from scratch, like its cost sum).
+template <int MODEL, int FAST, bool GEN, bool UC, bool AC = false>
 __device__ __forceinline__ float lane_cost(const float4* __restrict__ np, uint64_t gi, const GenCtx& gen, const float4* mp,
                                            const float* s_ktab, const float* __restrict__ x0, const Dims& d,
-                                           const ModelCtx& ctx) {
+                                           const ModelCtx& ctx, const float4* g4 = nullptr, const float* kappa = nullptr) {
     using M = ModelT<MODEL, FAST>;
     bool bad = false;
     float total;
     if constexpr (FAST != 0 && EntryGeneral<M>::value) {
         if (!M::start_in_box(ctx, x0))  // launch-uniform (x0 is shared): the copy whose first stage cost is bounds-tested
-            return trajectory_cost<MODEL, FAST, GEN, UC, false, true>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad);
+            return trajectory_cost<MODEL, FAST, GEN, UC, false, true, AC>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa);
     }
     // (racing, fast math: the unit wheel base of the reference is a launch-uniform branch around two copies of the loop)
     if (MODEL == MPPI_MODEL_RACING && FAST != 0 && ctx.unit_L)
-        total = trajectory_cost<MODEL, FAST, GEN, UC, true>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad);
+        total = trajectory_cost<MODEL, FAST, GEN, UC, true, false, AC>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa);
     else
-        total = trajectory_cost<MODEL, FAST, GEN, UC>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad);
+        total = trajectory_cost<MODEL, FAST, GEN, UC, false, false, AC>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa);
     if constexpr (FAST != 0 && !EntryGeneral<M>::value) {
         if (bad) {  // a fast path left its validity range: redo this lane with the library math
             bool ignore = false;
-            total = trajectory_cost<MODEL, 0, GEN, false>(np, gi, gen, mp, s_ktab, x0, d, ctx, ignore);
+            total = trajectory_cost<MODEL, 0, GEN, false, false, false, AC>(np, gi, gen, mp, s_ktab, x0, d, ctx, ignore, g4, kappa);
         }
     }
     return total;
@@ -237,97 +259,27 @@ __device__ __forceinline__ void batch1_rollout(const ModelCtx& ctx, const float*
 #ifndef MPPI_ROLLOUT_ATTR
 #define MPPI_ROLLOUT_ATTR  // e.g. __attribute__((amdgpu_waves_per_eu(8))) for occupancy experiments
 #endif
-template <int MODEL, int FAST, bool GEN, bool UC>
-__global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void rollout_cost_kernel(const float4* __restrict__ noise,
-                                                             const float* __restrict__ mean,
-                                                             const float* __restrict__ x0,
-                                                             float* __restrict__ costs,
-                                                             unsigned* __restrict__ min_key,
-                                                             unsigned* __restrict__ next_min_key,
-                                                             float* __restrict__ mean_used,
-                                                             float* __restrict__ x0_used, Dims d, GenCtx gen,
-                                                             ModelCtx ctx, const float* __restrict__ b1_in,
-                                                             float* __restrict__ b1_state_out,
-                                                             unsigned long long* __restrict__ stamps) {
-    using M = ModelT<MODEL, FAST>;
-    __shared__ float s_min[BLOCK / WAVE];
-    // `stamps` (or null: untimed) is the launch's pair of 100 MHz wall-clock stamps {start, end} (StageTimer): block 0, which
-    // is dispatched first, stores the start; every block raises the end as its last act.  end - start runs from block 0's
-    // first instruction to the last block's last one: the stage's time as seen from inside the dispatch.
-    // The pointer waits for the end of the block in LDS, not in a pair of SGPRs held across the horizon loop: six more live
-    // SGPRs took the kernel from eight waves per SIMD to seven.  `costs` and `min_key` wait there too: the loop's second
-    // bound (trajectory_cost, "Even drain") needs the registers (racing: 103 SGPRs and seven waves per SIMD without, 99 with).
-    ROLLOUT_TRACE(0);
-    ROLLOUT_TRACE(5);
-    __shared__ unsigned long long* s_stamps;
-    __shared__ float* s_costs;
-    __shared__ unsigned* s_min_key;
-    if (threadIdx.x == 0) {
-        s_stamps = stamps;
-        s_costs = costs;
-        s_min_key = min_key;
-        if (stamps != nullptr && blockIdx.x == 0) stamps[0] = wall_clock64();
-    }
-    // [4*R] mean groups, [4*R] zeros (samples that do not inherit the mean), then [T*KROW] step rows
-    extern __shared__ __attribute__((aligned(16))) float s_dyn[];
-    // One extra block (the last) when the PREVIOUS solve left its state sequence pending (option "lazy_state_seq"): the
-    // batch-1 rollout of that solution (mppi.py:448-449) from the inputs finalize_kernel left in b1_in — T dependent steps
-    // of one wave, hidden behind this launch's N-sample rollout instead of extending the previous solve's tail.
-    if (b1_state_out != nullptr && blockIdx.x == gridDim.x - 1) {
-        for (int i = threadIdx.x; i < d.row + M::DS; i += BLOCK) s_dyn[i] = b1_in[i];
-        __syncthreads();
-        batch1_rollout<MODEL, FAST>(ctx, s_dyn + d.row, s_dyn, d.T, b1_state_out);
-        if (stamps != nullptr && threadIdx.x == 0) (void)atomicMax(stamps + 1, (unsigned long long)wall_clock64());
-        return;
-    }
-#ifdef MPPI_AB_VGPR_FLOOR  // (A/B knob of scripts/build_variant.sh: same code at the occupancy of an 85-VGPR build)
-    asm volatile("; vgpr floor" ::: "v84");
-#endif
-    // the state this solve starts from outlives the caller's buffer (mppi_bind_state is zero-copy): later
-    // re-rolls of this solve's samples (get_top_samples, _state_seq_batch) read the snapshot
-    if (blockIdx.x == 0 && threadIdx.x < M::DS) x0_used[threadIdx.x] = x0[threadIdx.x];
-    float4* s_mean4 = reinterpret_cast<float4*>(s_dyn);
-    float* s_ktab = s_dyn + 8 * d.R;
-    for (int f = threadIdx.x; f < 4 * d.R; f += BLOCK) {
-        const float m = f < d.row ? mean[f] : 0.0f;
-        s_dyn[f] = m;
-        s_dyn[4 * d.R + f] = 0.0f;
-        // the mean this solve samples around outlives the warm-start update (get_top_samples re-rolls with it)
-        if (blockIdx.x == 0 && f < d.row) mean_used[f] = m;
-    }
-    for (int f = threadIdx.x; f < d.T * M::KROW; f += BLOCK) s_ktab[f] = ctx.ref[f];
-    __syncthreads();
-    ROLLOUT_TRACE(1);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int64_t tile = (int64_t)blockIdx.x * (BLOCK / WAVE) + wid;
-    // the minimum key is double-buffered: this launch accumulates into `min_key` (reset by the
-    // previous launch) and resets the other slot for the next one -> no memset between solves
-    if (blockIdx.x == 0 && threadIdx.x == 0) *next_min_key = 0xFFFFFFFFu;
-    float total = INFINITY;
-    if (tile < d.tiles) {
-        const int64_t i = tile * 64 + lane;
-        const uint64_t gi = (uint64_t)(d.sample_offset + i);
-        const bool inherit = (d.sample_offset + i) < d.inherit_count;
-        const float4* np = noise + tile * d.R * 64 + lane;
-        bool bad = false;
-        const float4* mp = inherit ? s_mean4 : s_mean4 + d.R;
-        total = lane_cost<MODEL, FAST, GEN, UC>(np, gi, gen, mp, s_ktab, x0, d, ctx);
-        if (i < d.N) s_costs[i] = total;
-        else total = INFINITY;
-    }
-    const float wm = wave_min(total);
-    if (lane == 0) s_min[wid] = wm;
-    __syncthreads();
-    ROLLOUT_TRACE(4);
-    if (threadIdx.x == 0) {
-        float m = s_min[0];
-#pragma unroll
-        for (int w = 1; w < BLOCK / WAVE; ++w) m = fminf(m, s_min[w]);
-        if (m < INFINITY) atomicMin(s_min_key, float_to_key(m));
-        unsigned long long* const st = s_stamps;
-        if (st != nullptr) (void)atomicMax(st + 1, (unsigned long long)wall_clock64());
-    }
-}
+
+// Launch arguments of the control-cost term (rollout_action_cost_kernel, action_cost_kernel)
+struct ActionCostArgs {
+    const float* sigtab;      // per-column sigma [4R] (the adapted table / a wide handle's), or null: d.sigma[k]
+    const float* lambda_dev;  // the temperature in device memory, or null: `lambda`
+    float lambda;             // (0: no temperature yet — the term is zero)
+    float weight;             // action_cost_weight
+};
+
+// rollout_cost_kernel<MODEL, FAST, GEN, UC> and, with the control-cost term (one more argument: ActionCostArgs),
+// rollout_action_cost_kernel<MODEL, FAST, GEN, UC>: one text, compiled twice (mppi_rollout_kernel.inc says why).
+#define MPPI_ROLLOUT_KERNEL rollout_cost_kernel
+#define MPPI_ROLLOUT_AC 0
+#include "mppi_rollout_kernel.inc"
+#undef MPPI_ROLLOUT_KERNEL
+#undef MPPI_ROLLOUT_AC
+#define MPPI_ROLLOUT_KERNEL rollout_action_cost_kernel
+#define MPPI_ROLLOUT_AC 1
+#include "mppi_rollout_kernel.inc"
+#undef MPPI_ROLLOUT_KERNEL
+#undef MPPI_ROLLOUT_AC
 
 // ------------------------------------------------------------------------------------------
 // The north star's literal mapping, kept for comparison (mppi_set_option("mapping", 1)): ONE WAVEFRONT

@@ -294,3 +294,25 @@ def check_covariance_args(adapt_covariance, cov_rate, cov_floor, sigma_min, sigm
         raise ValueError("adapt_covariance=True is not available with noise_source='torch_cpu': every draw would need the "
                          "sigma table on the host")
     return rate, floor, smin, smax
+
+
+def check_action_cost_args(action_cost, action_cost_weight, sigmas, adapt_covariance=False, cov_floor=1e-6, sigma_min=None):
+    """Validate the keyword arguments of the control-cost term of MPPI (src/pi_mpc/mppi.py:294-316,330-336) and return the
+    weight as a float.  ValueError for a negative or non-finite weight and, with the term on, for any sigmas[k] <= 0
+    (the term divides by sigma^2) and for adapt_covariance=True with cov_floor == 0 and no positive sigma_min in every
+    dimension (the adapted table could reach 0 and its inverse overflow)."""
+    w = float(action_cost_weight)
+    if not (w >= 0.0 and np.isfinite(w)):
+        raise ValueError(f"action_cost_weight must be finite and >= 0, got {action_cost_weight}")
+    if not action_cost:
+        return w
+    s = np.asarray(sigmas.detach().cpu() if hasattr(sigmas, "detach") else sigmas, dtype=np.float32).reshape(-1)
+    if not np.all(s > 0.0):
+        raise ValueError("action_cost=True needs sigmas > 0 in every control dimension (the term divides by sigma^2)")
+    if adapt_covariance and not float(cov_floor) > 0.0:
+        smin = None if sigma_min is None else np.asarray(
+            sigma_min.detach().cpu() if hasattr(sigma_min, "detach") else sigma_min, dtype=np.float32).reshape(-1)
+        if smin is None or not np.all(smin > 0.0):
+            raise ValueError("action_cost=True with adapt_covariance=True needs cov_floor > 0 or a positive sigma_min in every "
+                             "control dimension: the adapted sigma table could reach 0")
+    return w

@@ -20,7 +20,7 @@ class ModuleProtocolMixin:
         """A second solver that continues EXACTLY like this one: same constructor arguments, a handle of its own, and every
         piece of dynamic state copied on the device (mppi_clone_state: warm start, noise identity, the last solve's costs,
         Savitzky-Golay history, the temperature and the device-resident search / dual state, model parameters, maps,
-        reference window and path index, options, the sigma table and settings of the covariance adaptation) or on the host (RNG stream position, the torch-CPU generator, temperatures
+        reference window and path index, options, the sigma table and settings of the covariance adaptation, the control-cost term's switch and weight) or on the host (RNG stream position, the torch-CPU generator, temperatures
         already fetched).  The callables are deep-copied like the reference's attributes would be — with them the environment
         / controller objects that own the model's parameters — and the native tags re-resolved on the copies."""
         if self._world > 1 or self._force_exchange:

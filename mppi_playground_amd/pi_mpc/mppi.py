@@ -91,6 +91,8 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         cov_floor: float = 1e-6,
         sigma_min: Optional[torch.Tensor] = None,
         sigma_max: Optional[torch.Tensor] = None,
+        action_cost: bool = False,
+        action_cost_weight: float = 1.0,
         _force_exchange: bool = False,
     ) -> None:
         """Arguments up to `seed` are the reference's (src/pi_mpc/mppi.py:24-47).
@@ -155,6 +157,20 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                 state_dict() carry it.  The noise is then always materialised (like set_option("noise_regen", 0)) and small
                 problems take the multi-kernel path.  Not with shard_samples=True (the variance would need a second
                 exchange) or noise_source="torch_cpu" (every draw would need the table on the host): ValueError.
+            action_cost: OPT-IN (default False: the costs are the stage + terminal costs, bit for bit as before, and nothing
+                else is launched).  True: the control-cost term the reference computes on every solve at mppi.py:294-316
+                (`action_costs[:, t] = mean_action_seq[t] @ inv_covariance[t] @ U[:, t].T`) and leaves commented out of the
+                cost sum at mppi.py:330-336 — cost_i += action_cost_weight * lambda * sum_t mean[t] @ inv_cov[t] @ U_i[t].
+                Literal to the reference: row 0 of the inverse covariance is zero (mppi.py:135-136 fill t = 1..T-1), U is
+                the solver-clamped perturbed action, and `mean` is the real warm start for every sample — the exploration
+                samples, which do not inherit it when sampling, included.  lambda is `_lambda` as the rollout finds it: the
+                fixed value; under ESSPS / LBPS the previous solve's temperature, under MPO the dual's current one (0 while
+                a rule has produced none: the warm start of a first solve is zero anyway).  With adapt_covariance the
+                inverse follows `sigma_seq`.  action_cost_weight = 1 is the sketch; the paper scales the term by 1 - alpha.
+                `_costs`, the temperature rules, the weights and get_top_samples see the sum.  Native models carry the term
+                inside the rollout kernel (instantiations of their own; small problems take the multi-kernel path), opaque
+                callables get it from one extra small kernel per solve.  ValueError for a negative weight, sigmas <= 0,
+                or adapt_covariance with cov_floor = 0 and no positive sigma_min.
             shard_samples: treat `num_samples` as the GLOBAL sample count and let this rank own the
                 contiguous block rank*N/W .. (rank+1)*N/W of it (torch.distributed must be
                 initialised); the 4+T*dc-float shard summaries are exchanged once per solve with one RCCL
@@ -177,7 +193,7 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                           lbps_search=lbps_search, recognize_closures=recognize_closures, sg_filter=sg_filter,
                           graph_callables=graph_callables, lazy_state_seq=lazy_state_seq, adapt_covariance=adapt_covariance,
                           cov_rate=cov_rate, cov_floor=cov_floor, sigma_min=sigma_min, sigma_max=sigma_max,
-                          _force_exchange=_force_exchange)
+                          action_cost=action_cost, action_cost_weight=action_cost_weight, _force_exchange=_force_exchange)
         assert u_min.shape == (dim_control,)
         assert u_max.shape == (dim_control,)
         assert sigmas.shape == (dim_control,)
@@ -186,6 +202,9 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         self._adapt_covariance = bool(adapt_covariance)
         self._cov_rate, self._cov_floor, self._sigma_min, self._sigma_max = _host.check_covariance_args(
             adapt_covariance, cov_rate, cov_floor, sigma_min, sigma_max, dim_control, shard_samples, noise_source)
+        self._action_cost = bool(action_cost)
+        self._action_cost_weight = _host.check_action_cost_args(action_cost, action_cost_weight, sigmas, adapt_covariance,
+                                                                cov_floor, sigma_min)
         dev = torch.device(device)
         if dev.type != "cuda":
             raise ValueError(f"device={dev}: this MPPI runs its hot path on MI355X only; there is no CPU path "
@@ -338,6 +357,8 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             f = lambda a: (C.c_float * dim_control)(*[float(v) for v in a])  # noqa: E731
             self._h.call("mppi_set_covariance_adaptation", 1, self._cov_rate, self._cov_floor, f(self._sigma_min),
                          f(self._sigma_max))
+        if self._action_cost:  # mppi.py:294-316,330-336
+            self._h.call("mppi_set_action_cost", 1, self._action_cost_weight)
         # the LBPS search and the MPO step run inside the library (no interpreter work per probe) whenever the
         # statistics come from this device alone; sharded solvers combine the shards' statistics in Python
         self._search_in_library = auto_lambda_stats == "device" and self._world == 1
@@ -914,12 +935,25 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             self._h.call("mppi_rollout_actions", _ptr(self._action_out), 1, None, _ptr(self._state_out), st)
         self._actions_history_for_sg = np.concatenate([self._actions_history_for_sg[1:], a[0][None, :]])
 
+    def _action_cost_lambda(self) -> float:
+        """`self._lambda` as the reference's cost sum would read it (mppi.py:335, BEFORE this solve's temperature rule): the
+        marker for "the temperature in device memory" under a device-resident rule, else the float this solver holds (0
+        while a rule has produced none: the reference would multiply by the rule's name there)."""
+        if self._lambda_override is not None:
+            return float(self._lambda_override)
+        if self._rule_on_device is not None:
+            return _capi.LAMBDA_DEVICE
+        v = self._lambda_value
+        return float(v) if isinstance(v, (int, float)) and v > 0 else 0.0
+
     # ---- the strategies
     def _solve_by_steps(self, state, info):
         """A native model through the individual entry points (same kernels as mppi_solve)."""
         st = self._stream()
         self._bind_state(state, st)
         self._draw_noise(st)
+        if self._action_cost:
+            self._h.call("mppi_set_action_cost_lambda", self._action_cost_lambda())
         self._h.call("mppi_rollout_cost", st)  # Steps 1b-3: clamp, rollout, costs (src/pi_mpc/mppi.py:266-336)
         lam = self._temperature(st)
         summaries, nsh = self._reduce_and_exchange(lam, st)
@@ -939,6 +973,8 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         self._bind_state(state, st)
         self._draw_noise(st)
         self._generic_rollout_costs(state, info)  # Steps 1b-3 with the callables; the summed costs go back to the library
+        if self._action_cost:  # (outside the captured callables: one small kernel over the noise tiles)
+            self._h.call("mppi_add_action_cost", self._action_cost_lambda(), st)
         lam = self._temperature(st)
         summaries, nsh = self._reduce_and_exchange(lam, st)
         self._covariance_step(lam, st)  # after the library reduction, before the warm start replaces this solve's mean
