@@ -101,7 +101,7 @@ typedef struct MppiConfig {
 const char* mppi_version(void);
 /* Integer version of THIS header's function signatures; bindings compare it with the constant they were written
  * against and refuse a stale library (a changed argument list would otherwise be called with shifted arguments). */
-#define MPPI_ABI_VERSION 12
+#define MPPI_ABI_VERSION 13
 int mppi_abi_version(void);
 /* Number of visible HIP devices (0 => the product cannot run; callers must fail loudly). */
 int mppi_device_count(void);
@@ -316,6 +316,27 @@ int mppi_set_sigma_table(mppi_handle_t h, const float* table, int on_device, voi
 int mppi_set_action_cost(mppi_handle_t h, int enable, float weight);
 int mppi_set_action_cost_lambda(mppi_handle_t h, float lambda /* >= 0, or MPPI_LAMBDA_DEVICE */);
 int mppi_add_action_cost(mppi_handle_t h, float lambda /* >= 0, or MPPI_LAMBDA_DEVICE */, void* stream);
+/* Temporally correlated sampling noise — an AR(1) filter along the horizon (the colored noise of iCEM and of the
+ * low-frequency-sampling MPPI variants; the reference draws independent steps).  Opt-in; off, nothing changes and nothing else
+ * is launched.  For sample i and control dimension k, with xi[t] the standard normal every solve draws for (i, t, k) (Philox /
+ * Box-Muller, counter (global sample index, float4 group, solve index): the filtered and the unfiltered stream of one seed
+ * consume the same normals), in fp32 with one rounding per operation:
+ *     z[0] = xi[0],   z[t] = beta[k] * z[t-1] + alpha[k] * xi[t]  (t = 1..T-1),   alpha[k] = (float)sqrt(1 - (double)beta[k]^2)
+ *     eps[i][t][k] = z[t] * s[t][k]     (s: `sigmas`, or the per-step sigma table while the covariance adaptation is on)
+ * The start is stationary and the scale comes after the filter: every step keeps the marginal standard deviation s[t][k], the
+ * lag-1 correlation is beta[k].  Exploration samples are filtered like the others; the filter never crosses samples, so
+ * sharded handles draw the rows of the unsharded solve.  While it is on the noise is always materialised as tiles, by
+ * sample_colored_kernel (the handle behaves like "noise_regen" = 0 whatever the option says, exactly as under the covariance
+ * adaptation: mppi_solve takes the multi-kernel sequence and mppi_fused_geometry reports 0 / 0; candidates of other shards
+ * cannot be re-rolled) and mppi_sample_posterior draws through the same filter.  Injected noise (mppi_inject_noise) is taken
+ * as it is.
+ *   mppi_set_noise_correlation  beta_host [dim_control], each in [0, 1) (else MPPI_E_INVALID); NULL or all zero: off.  Allowed
+ *                         between solves; noise tiles that were not injected are dropped.  MPPI_E_STATE before
+ *                         mppi_set_control_limits where that call is required.  Copied by mppi_clone_state.  Set-up path:
+ *                         synchronises.
+ *   mppi_get_noise_correlation  the current beta [dim_control] (zeros while off). */
+int mppi_set_noise_correlation(mppi_handle_t h, const float* beta_host /* [dim_control]; NULL or all zero: off */);
+int mppi_get_noise_correlation(mppi_handle_t h, float* beta_out_host);
 /* Lazily completed state sequences (mppi_set_option("lazy_state_seq", 1)).  The reference returns `state_seq` — the batch-1
  * rollout of the solution, mppi.py:448-449,508-524 — with the action sequence, but nothing on a control loop's critical
  * path needs it: the next solve samples around the mean, env.step applies a[0].  With the option set, mppi_finalize /

@@ -23,7 +23,7 @@ LAMBDA_DEVICE = -1.0  # MPPI_LAMBDA_DEVICE: "the temperature a device-resident r
 AUTO_RULES = {None: 0, "ESSPS": 1, "LBPS": 2, "MPO": 3}  # MPPI_AUTO_*
 
 # every symbol include/mppi_hip.h declares
-ABI_VERSION = 12  # MPPI_ABI_VERSION of the header this binding was written against
+ABI_VERSION = 13  # MPPI_ABI_VERSION of the header this binding was written against
 
 SYMBOLS = [
     "mppi_version", "mppi_abi_version", "mppi_device_count", "mppi_last_error", "mppi_create", "mppi_destroy", "mppi_set_control_limits",
@@ -38,6 +38,7 @@ SYMBOLS = [
     "mppi_search_passes", "mppi_grid_lookup", "mppi_mpo_log_temperature_ptr", "mppi_join_state_seq", "mppi_state_seq_serial", "mppi_get_state_seq_timing", "mppi_comm_info",
     "mppi_set_covariance_adaptation", "mppi_update_covariance", "mppi_get_sigma_table", "mppi_set_sigma_table",
     "mppi_set_action_cost", "mppi_set_action_cost_lambda", "mppi_add_action_cost",
+    "mppi_set_noise_correlation", "mppi_get_noise_correlation",
 ]
 
 
@@ -157,6 +158,8 @@ def load():
     lib.mppi_set_action_cost.argtypes = [vp, i32, f32]
     lib.mppi_set_action_cost_lambda.argtypes = [vp, f32]
     lib.mppi_add_action_cost.argtypes = [vp, f32, vp]
+    lib.mppi_set_noise_correlation.argtypes = [vp, vp]
+    lib.mppi_get_noise_correlation.argtypes = [vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the .so does not export what the header declares
         if name not in ("mppi_version", "mppi_last_error"):

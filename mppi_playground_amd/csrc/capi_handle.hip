@@ -272,6 +272,9 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
         CLONE(cov.lim);
     }
     dst->cov.on = src->cov.on; dst->cov.rate = src->cov.rate; dst->cov.floor = src->cov.floor; dst->cov.ready = false;
+    // the noise correlation: the setting (its table is rebuilt from it; dst's tile bookkeeping follows below)
+    if (src->color.on || dst->color.on)
+        if (int rc = mppi_set_noise_correlation(dst, src->color.on ? src->color.beta.data() : nullptr)) return rc;
     dst->ac = src->ac;  // the control-cost term: switch, weight and the temperature of the next stand-alone rollout
     CLONE(core.mean);
     CLONE(core.mean_used);
@@ -413,9 +416,9 @@ int mppi_set_option(mppi_handle_t h, const char* key, int64_t value) {
         h->xchg.comm_enabled = value != 0;
         return MPPI_OK;
     }
-    if (k == "noise_regen") {  // (under covariance adaptation the tiles are the noise whatever this says: they stay)
+    if (k == "noise_regen") {  // (under covariance adaptation or a noise correlation the tiles are the noise whatever this says: they stay)
         o.noise_regen = value ? 1 : 0;
-        h->core.tiles_valid = h->core.tiles_valid && (h->core.injected || h->cov.on);
+        h->core.tiles_valid = h->core.tiles_valid && (h->core.injected || tiles_only(h));
         return MPPI_OK;
     }
     return fail(h, MPPI_E_INVALID, "unknown option " + k);

@@ -94,7 +94,8 @@ static bool fold_fits(mppi_handle_t h) {
 static int materialize_tiles(mppi_handle_t h, StageTimer& tm) {
     const unsigned grid = (unsigned)((h->d.tiles + 3) / 4);
     if (!h->limits_set) return fail(h, MPPI_E_STATE, "dim_control > 4: call mppi_set_control_limits first");
-    if (h->wide || h->cov.on) tm.launch(sample_kernel<true>, dim3(grid), dim3(BLOCK), 0, h->core.noise, h->d, h->core.gen, (const float*)sigma_table(h));
+    if (h->color.on) { if (int rc = sample_colored(h, tm)) return rc; }  // the filtered draw (always through the per-column tables)
+    else if (h->wide || h->cov.on) tm.launch(sample_kernel<true>, dim3(grid), dim3(BLOCK), 0, h->core.noise, h->d, h->core.gen, (const float*)sigma_table(h));
     else tm.launch(sample_kernel<false>, dim3(grid), dim3(BLOCK), 0, h->core.noise, h->d, h->core.gen, (const float*)nullptr);
     HIP_TRY(h, hipGetLastError());
     h->core.tiles_valid = true;
@@ -276,7 +277,7 @@ int mppi_sample(mppi_handle_t h, uint32_t solve_idx, void* stream) {
     h->core.gen.solve_idx = solve_idx;
     h->core.injected = false;
     h->core.tiles_valid = false;
-    if (h->opt.noise_regen && !h->wide && !h->cov.on) return MPPI_OK;  // consumers regenerate eps(seed, solve, i, t, k) in registers
+    if (h->opt.noise_regen && !h->wide && !tiles_only(h)) return MPPI_OK;  // consumers regenerate eps(seed, solve, i, t, k) in registers
     StageTimer tm(h, 0, s);
     return materialize_tiles(h, tm);
 }
@@ -335,7 +336,7 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
         return MPPI_OK;
     }
     StageTimer tm(h, 1, s, true);  // (this stage's one kernel stamps its own time)
-    const bool gen = h->opt.noise_regen && !h->core.injected && !h->cov.on;
+    const bool gen = h->opt.noise_regen && !h->core.injected && !tiles_only(h);
     if (!gen && !h->core.tiles_valid) return fail(h, MPPI_E_STATE, "no noise: call mppi_sample or mppi_inject_noise first");
     h->seq.min_slot ^= 1;
     unsigned* mk = h->core.min_key + h->seq.min_slot;

@@ -74,7 +74,7 @@ static int check_row_lds(mppi_handle_t h, const void* kernel, size_t dyn, const 
 // h->topk.cand when k > TOPK_MAX (sorted in place).
 static int topk_rollout(mppi_handle_t h, const unsigned long long* cand, int k, float lambda, float* states_out,
                         float* weights_out, bool clean, bool need_local, hipStream_t s, bool direct = false) {
-    const bool gen = h->opt.noise_regen && !h->core.injected && !h->cov.on;
+    const bool gen = h->opt.noise_regen && !h->core.injected && !tiles_only(h);
     if (!gen && !h->core.tiles_valid) return fail(h, MPPI_E_STATE, "no noise: solve first");
     if (!gen && !need_local)
         return fail(h, MPPI_E_STATE, "candidates of other shards can only be re-rolled from regenerated noise (noise_regen = 1, no injection)");
@@ -118,7 +118,9 @@ int mppi_sample_posterior(mppi_handle_t h, uint32_t solve_idx, const float* loc_
     if (!h->limits_set) return fail(h, MPPI_E_STATE, "dim_control > 4: call mppi_set_control_limits first");
     const GenCtx g{h->core.gen.seed_lo, h->core.gen.seed_hi, solve_idx};
     const unsigned grid = (unsigned)(((int64_t)k * h->d.R + BLOCK - 1) / BLOCK);
-    if (h->wide || h->cov.on)  // sigma per column: the table the solves draw from (mppi.py:416-418: `_noise_distribution` follows the covariance)
+    if (h->color.on) {  // the filter of the solves' draw (`_noise_distribution` is what the posterior follows)
+        if (int rc = posterior_colored(h, g, loc_dev, k, samples_out_dev, (hipStream_t)stream)) return rc;
+    } else if (h->wide || h->cov.on)  // sigma per column: the table the solves draw from (mppi.py:416-418: `_noise_distribution` follows the covariance)
         hipLaunchKernelGGL(posterior_sample_kernel<true>, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, loc_dev, k,
                            samples_out_dev, h->d, g, (const float*)sigma_table(h));
     else

@@ -15,10 +15,12 @@
 //   capi_topk.hip      queries after a solve                                         (mppi_topk.hpp)
 //   capi_exchange.hip  RCCL loader, comm / p2p exchanges, time-out flags             (+ the p2p kernels)
 //   capi_covariance.hip  covariance adaptation: settings, the per-step sigma table, the step after the weights (mppi_variance.hpp)
+//   capi_colored.hip   temporally correlated noise: the setting, its per-column table, the filtered draws (mppi_sample.hpp)
 // Kernel headers, one per stage.  A kernel that is not a template is defined in the one unit that launches it.
 //   mppi_common.hpp    Dims, GenCtx, wave reductions
 //   mppi_cells.hpp     the tagged 8-byte cell: how blocks of one launch and peer devices hand values over (search, fused, exchange)
-//   mppi_sample.hpp    step 1: the noise stream (gen_noise4), sample_kernel, posterior draws
+//   mppi_sample.hpp    step 1: the noise stream (gen_noise4), sample_kernel, posterior draws; opt-in: sample_colored_kernel,
+//                      posterior_colored_kernel (mppi_colored.hpp: the scalar rule of the AR(1) filter)
 //   mppi_rollout.hpp   steps 1b-3: rollout_cost_kernel (THE hot loop: trajectory_cost), the wavefront-per-trajectory variant
 //   mppi_reduce.hpp    steps 5-6: weights_reduce_kernel
 //   mppi_variance.hpp  after steps 5-6, opt-in: weighted_variance_kernel, sigma_update_kernel (mppi_covariance.hpp: the scalar rule)
@@ -198,6 +200,14 @@ struct MppiSolver {
         DevBuf<float> live;            // [REDUCE_MAX_BLOCKS] which of them were published
         bool ready = false;            // mppi_weights_reduce ran and mppi_finalize has not yet: the step may run
     } cov;
+
+    // temporally correlated noise (capi_colored.hip; mppi_colored.hpp is the rule).  While `on`, the noise is drawn by
+    // sample_colored_kernel and always materialised as tiles (the handle behaves like noise_regen = 0, as under cov.on).
+    struct Color {
+        bool on = false;
+        std::vector<float> beta;       // [dc] lag-1 correlation per control dimension (empty: never set, all zero)
+        DevBuf<float> tab;             // per-column {beta[4R], alpha[4R]}, zeros past the row
+    } color;
 
     // the control-cost term (mppi.py:294-316,330-336; mppi_set_action_cost): cost_i += weight * lambda * A_i
     struct ActionCost {
@@ -516,12 +526,19 @@ int reserve_ref(mppi_handle_t h, int rows);
 
 // the per-column sigma table the sampler reads (see MppiSolver::Cov)
 inline float* sigma_table(mppi_handle_t h) { return h->wide ? h->core.coltab.p : h->cov.sigtab.p; }
+// the noise of this handle exists as materialised tiles only, whatever option "noise_regen" says: sigma comes per step from
+// the adapted table, or the draw carries a filter along the horizon (the regenerating consumers know neither)
+inline bool tiles_only(mppi_handle_t h) { return h->cov.on || h->color.on; }
 // regenerate the noise in registers?  Not when it was injected, nor when sigma comes per column from a table
-inline bool regen_noise(mppi_handle_t h) { return h->opt.noise_regen && !h->core.injected && !h->wide && !h->cov.on; }
+inline bool regen_noise(mppi_handle_t h) { return h->opt.noise_regen && !h->core.injected && !h->wide && !tiles_only(h); }
 
 // capi_covariance.hip
 int cov_alloc(mppi_handle_t h);
 int fill_sigma_table(mppi_handle_t h, const float* sigmas, int n);
+
+// capi_colored.hip: the correlated forms of the tile draw (one launch of the stage `tm`) and of the posterior draw
+int sample_colored(mppi_handle_t h, StageTimer& tm);
+int posterior_colored(mppi_handle_t h, const GenCtx& g, const float* loc_dev, int k, float* samples_out_dev, hipStream_t s);
 
 // capi_solve.hip
 int resolve_lambda(mppi_handle_t h, float lambda, const float** lam_dev);

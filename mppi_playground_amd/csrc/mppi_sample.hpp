@@ -1,6 +1,8 @@
-// mppi_sample.hpp — Step 1 (mppi.py:255-263): the device noise stream (gen_noise4 is its definition), sample_kernel, posterior draws.
+// mppi_sample.hpp — Step 1 (mppi.py:255-263): the device noise stream (gen_noise4 is its definition), sample_kernel, posterior
+// draws, and their temporally correlated forms (sample_colored_kernel, posterior_colored_kernel).
 // Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
+#include "mppi_colored.hpp"
 #include "mppi_common.hpp"
 
 namespace mppi {
@@ -73,6 +75,120 @@ __global__ __launch_bounds__(BLOCK) void posterior_sample_kernel(const float* __
     for (int j = 0; j < 4; ++j) {
         const int f = 4 * r + j;
         if (f < d.row) samples[(int64_t)q * d.row + f] = loc[f] + nv[j];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Temporally correlated noise (opt-in, mppi_set_noise_correlation; mppi_colored.hpp is the scalar rule): the standard normals
+// of one (sample, control dimension) run through z[t] = beta[k] z[t-1] + alpha[k] xi[t] along the horizon, z[0] = xi[0],
+// and only then meet sigma: eps[i][t][k] = z[t] * s[t][k].  xi is what gen_noise4 draws before its multiplication by sigma,
+// same counters, so the filtered and the unfiltered stream of one seed consume the same normals.  Column f = 4r + j of the
+// row is step f / dc of dimension f % dc: the filter links column f to column f - dc, inside a float4 group as well as
+// across groups.  sigma, beta and alpha come per column from tables of 4R entries built on the host (zeros past the row:
+// those columns come out as 0), wave-uniform reads, one code path for every dim_control.
+__device__ __forceinline__ void gen_normal4(uint64_t gi, int r, const GenCtx& g, float (&z)[4]) {
+    const u32x4 x = noise_bits(gi, r, g);
+    box_muller(x.x, x.y, z[0], z[1]);
+    box_muller(x.z, x.w, z[2], z[3]);
+}
+// dim_control <= 4: `carry` holds the filtered normals of the last DC columns, oldest first (registers; starts as zeros).
+// z: xi of group r on entry, the filtered normals on return.  `coef` = {beta[C], alpha[C]}, C = 4R.
+template <int DC>
+__device__ __forceinline__ void colored_group_carry(float (&z)[4], int r, const float* __restrict__ coef, int C, float (&carry)[DC]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int f = 4 * r + j;
+        const float zn = f < DC ? z[j] : colored_step(carry[0], z[j], coef[f], coef[C + f]);
+#pragma unroll
+        for (int i = 0; i + 1 < DC; ++i) carry[i] = carry[i + 1];
+        carry[DC - 1] = zn;
+        z[j] = zn;
+    }
+}
+// dim_control > 4: column f - dc lies in an earlier group, which the caller has stored already; `earlier(f)` reads it back.
+template <class Earlier>
+__device__ __forceinline__ void colored_group_readback(float (&z)[4], int r, int dc, const float* __restrict__ coef, int C, Earlier earlier) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int f = 4 * r + j;
+        if (f >= dc) z[j] = colored_step(earlier(f - dc), z[j], coef[f], coef[C + f]);
+    }
+}
+
+// sample_kernel's geometry and store pattern (one lane per trajectory, one wave per tile, lane-major 1 KiB stores); the lane
+// walks its groups in order and carries the filter.  DC = dim_control for 1..4.  DC = 0 is every wider row: the lane stores
+// its FILTERED NORMALS first and reads column f - dc back from the tile it has just written — the same thread loading from
+// the address it stored to, which a thread always sees in program order, so no fence or barrier is needed — and scales the
+// row by sigma in a second walk (the scaled value fl(z * s) would not give z back).
+template <int DC>
+__global__ __launch_bounds__(BLOCK) void sample_colored_kernel(float4* noise, Dims d, GenCtx g, const float* __restrict__ sig_cols,
+                                                               const float* __restrict__ coef) {
+    const int lane = threadIdx.x & 63;
+    const int64_t tile = (int64_t)blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6);
+    if (tile >= d.tiles) return;
+    const uint64_t gi = (uint64_t)(d.sample_offset + tile * 64 + lane);
+    float4* out = noise + tile * d.R * 64 + lane;
+    const int C = 4 * d.R;
+    float z[4];
+    if constexpr (DC > 0) {
+        float carry[DC] = {};
+        for (int r = 0; r < d.R; ++r) {
+            gen_normal4(gi, r, g, z);
+            colored_group_carry<DC>(z, r, coef, C, carry);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[j] *= sig_cols[4 * r + j];
+            out[(int64_t)r * 64] = make_float4(z[0], z[1], z[2], z[3]);
+        }
+    } else {
+        const auto earlier = [out](int f) {
+            const float4 p = out[(int64_t)(f >> 2) * 64];
+            const int j = f & 3;
+            return j == 0 ? p.x : j == 1 ? p.y : j == 2 ? p.z : p.w;
+        };
+        for (int r = 0; r < d.R; ++r) {
+            gen_normal4(gi, r, g, z);
+            colored_group_readback(z, r, d.dc, coef, C, earlier);
+            out[(int64_t)r * 64] = make_float4(z[0], z[1], z[2], z[3]);
+        }
+        for (int r = 0; r < d.R; ++r) {
+            const float4 p = out[(int64_t)r * 64];
+            const float* s = sig_cols + 4 * r;
+            out[(int64_t)r * 64] = make_float4(p.x * s[0], p.y * s[1], p.z * s[2], p.w * s[3]);
+        }
+    }
+}
+
+// posterior_sample_kernel through the same filter: one thread per sample walks its row (k is small).  DC as above; the wide
+// form keeps the filtered normals in the sample's own output row until its second walk.
+template <int DC>
+__global__ __launch_bounds__(BLOCK) void posterior_colored_kernel(const float* __restrict__ loc, int k, float* samples, Dims d, GenCtx g,
+                                                                  const float* __restrict__ sig_cols, const float* __restrict__ coef) {
+    const int q = blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= k) return;
+    float* row = samples + (int64_t)q * d.row;
+    const int C = 4 * d.R;
+    float z[4];
+    if constexpr (DC > 0) {
+        float carry[DC] = {};
+        for (int r = 0; r < d.R; ++r) {
+            gen_normal4((uint64_t)q, r, g, z);
+            colored_group_carry<DC>(z, r, coef, C, carry);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int f = 4 * r + j;
+                if (f < d.row) row[f] = loc[f] + z[j] * sig_cols[f];
+            }
+        }
+    } else {
+        const auto earlier = [row](int f) { return row[f]; };  // (f - dc < row for every column of the 4R, dc > 4)
+        for (int r = 0; r < d.R; ++r) {
+            gen_normal4((uint64_t)q, r, g, z);
+            colored_group_readback(z, r, d.dc, coef, C, earlier);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (4 * r + j < d.row) row[4 * r + j] = z[j];
+        }
+        for (int f = 0; f < d.row; ++f) row[f] = loc[f] + row[f] * sig_cols[f];
     }
 }
 

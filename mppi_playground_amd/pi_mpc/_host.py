@@ -316,3 +316,24 @@ def check_action_cost_args(action_cost, action_cost_weight, sigmas, adapt_covari
             raise ValueError("action_cost=True with adapt_covariance=True needs cov_floor > 0 or a positive sigma_min in every "
                              "control dimension: the adapted sigma table could reach 0")
     return w
+
+
+def check_noise_beta_args(noise_beta, dim_control, noise_source="philox", action_cost=False):
+    """Validate the `noise_beta` keyword argument of MPPI (the lag-1 correlation of the AR(1) filter on the sampling noise)
+    and return it as a float32 array [dim_control]: a float stands for every control dimension.  ValueError for a wrong
+    length, an entry outside [0, 1) and — with any entry non-zero — for the two combinations the filter does not support."""
+    b = np.asarray(noise_beta.detach().cpu() if hasattr(noise_beta, "detach") else noise_beta, dtype=np.float32)
+    if b.ndim == 0:
+        b = np.full(dim_control, b, np.float32)
+    b = np.ascontiguousarray(b.reshape(-1), np.float32)
+    if b.shape != (dim_control,):
+        raise ValueError(f"noise_beta must be a float or have shape ({dim_control},)")
+    if not np.all((b >= 0.0) & (b < 1.0)):
+        raise ValueError(f"noise_beta must lie in [0, 1) in every control dimension, got {noise_beta}")
+    if b.any() and noise_source == "torch_cpu":
+        raise ValueError("noise_beta > 0 is not available with noise_source='torch_cpu': the filter would need a second "
+                         "implementation on the host")
+    if b.any() and action_cost:
+        raise ValueError("noise_beta > 0 is not available with action_cost=True: the term's inverse covariance is diagonal in "
+                         "time and would no longer be the KL term of the distribution sampled from")
+    return b

@@ -20,7 +20,7 @@ class ModuleProtocolMixin:
         """A second solver that continues EXACTLY like this one: same constructor arguments, a handle of its own, and every
         piece of dynamic state copied on the device (mppi_clone_state: warm start, noise identity, the last solve's costs,
         Savitzky-Golay history, the temperature and the device-resident search / dual state, model parameters, maps,
-        reference window and path index, options, the sigma table and settings of the covariance adaptation, the control-cost term's switch and weight) or on the host (RNG stream position, the torch-CPU generator, temperatures
+        reference window and path index, options, the sigma table and settings of the covariance adaptation, the control-cost term's switch and weight, the noise correlation) or on the host (RNG stream position, the torch-CPU generator, temperatures
         already fetched).  The callables are deep-copied like the reference's attributes would be — with them the environment
         / controller objects that own the model's parameters — and the native tags re-resolved on the copies."""
         if self._world > 1 or self._force_exchange:
@@ -84,7 +84,7 @@ class ModuleProtocolMixin:
     def get_extra_state(self) -> Dict[str, Any]:
         """The solver's dynamic state for state_dict() (entry `_extra_state`; the reference keeps the same things as plain
         attributes, which its state_dict() silently drops): warm start, Savitzky-Golay history, RNG stream position (Philox
-        solve index and the torch-CPU generator), the adapted sigma table (adapt_covariance), the temperature and — MPO — the dual with its Adam moments."""
+        solve index and the torch-CPU generator), the adapted sigma table (adapt_covariance), the noise correlation (`noise_beta`), the temperature and — MPO — the dual with its Adam moments."""
         if self._lambda_pending:
             self._fetch_lambda()
         mean = torch.empty(self._horizon, self._dim_control, device=self._device, dtype=self._dtype)
@@ -95,6 +95,7 @@ class ModuleProtocolMixin:
                "cpu_generator": None if self._cpu_gen is None else self._cpu_gen.get_state(), "mpo": None}
         if self._adapt_covariance:  # the adapted per-step standard deviations
             out["sigma_seq"] = self.sigma_seq.cpu()
+        out["noise_beta"] = self.noise_beta
         if self._auto_lambda == "MPO":
             if self._rule_on_device == "MPO":
                 st4 = (C.c_double * 4)()
@@ -124,6 +125,8 @@ class ModuleProtocolMixin:
             sg = sg.to(self._device, self._dtype).contiguous()
             self._h.call("mppi_set_sigma_table", sg.data_ptr(), 1, self._stream())
             torch.cuda.current_stream(self._device).synchronize()
+        if state.get("noise_beta") is not None:  # (absent in a state written before the setting existed: it stays as constructed)
+            self.set_noise_beta(state["noise_beta"])
         if state.get("cpu_generator") is not None and self._cpu_gen is not None:
             self._cpu_gen.set_state(state["cpu_generator"])
         if state.get("mpo") is not None and self._auto_lambda == "MPO":

@@ -93,6 +93,7 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         sigma_max: Optional[torch.Tensor] = None,
         action_cost: bool = False,
         action_cost_weight: float = 1.0,
+        noise_beta=0.0,
         _force_exchange: bool = False,
     ) -> None:
         """Arguments up to `seed` are the reference's (src/pi_mpc/mppi.py:24-47).
@@ -171,6 +172,19 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                 inside the rollout kernel (instantiations of their own; small problems take the multi-kernel path), opaque
                 callables get it from one extra small kernel per solve.  ValueError for a negative weight, sigmas <= 0,
                 or adapt_covariance with cov_floor = 0 and no positive sigma_min.
+            noise_beta: OPT-IN (default 0: the noise is independent from step to step, bit for bit as before, and nothing else
+                is launched).  A float, or a sequence / tensor of dim_control floats, in [0, 1): the lag-1 correlation of an
+                AR(1) filter along the horizon (the colored noise of iCEM and of the low-frequency-sampling MPPI variants).  With
+                xi the standard normals the solve draws anyway, z[0] = xi[0], z[t] = beta[k] z[t-1] + sqrt(1 - beta[k]^2) xi[t],
+                eps[i,t,k] = z[t] * s[t,k]: every step keeps its standard deviation (`sigmas`, or `sigma_seq` under
+                adapt_covariance), exploration samples are filtered too, and the same seed consumes the same normals.
+                get_samples_from_posterior draws through the filter; inject_noise() is taken as it is.  `solver.noise_beta`
+                reads it, set_noise_beta() changes it between solves, reset() leaves it alone, deepcopy and state_dict() carry
+                it.  The noise is then always materialised (like set_option("noise_regen", 0)): a colored solve pays the
+                materialised-noise path, and small problems take the multi-kernel sequence.  Works with opaque callables,
+                adapt_covariance, every temperature rule and shard_samples=True.  Not with noise_source="torch_cpu" (the
+                filter would need a second implementation on the host) or action_cost=True (the term's inverse covariance
+                is diagonal in time): ValueError, as for a value outside [0, 1) or of the wrong length.
             shard_samples: treat `num_samples` as the GLOBAL sample count and let this rank own the
                 contiguous block rank*N/W .. (rank+1)*N/W of it (torch.distributed must be
                 initialised); the 4+T*dc-float shard summaries are exchanged once per solve with one RCCL
@@ -193,7 +207,8 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                           lbps_search=lbps_search, recognize_closures=recognize_closures, sg_filter=sg_filter,
                           graph_callables=graph_callables, lazy_state_seq=lazy_state_seq, adapt_covariance=adapt_covariance,
                           cov_rate=cov_rate, cov_floor=cov_floor, sigma_min=sigma_min, sigma_max=sigma_max,
-                          action_cost=action_cost, action_cost_weight=action_cost_weight, _force_exchange=_force_exchange)
+                          action_cost=action_cost, action_cost_weight=action_cost_weight, noise_beta=noise_beta,
+                          _force_exchange=_force_exchange)
         assert u_min.shape == (dim_control,)
         assert u_max.shape == (dim_control,)
         assert sigmas.shape == (dim_control,)
@@ -205,6 +220,7 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         self._action_cost = bool(action_cost)
         self._action_cost_weight = _host.check_action_cost_args(action_cost, action_cost_weight, sigmas, adapt_covariance,
                                                                 cov_floor, sigma_min)
+        self._noise_beta = _host.check_noise_beta_args(noise_beta, dim_control, noise_source, action_cost)
         dev = torch.device(device)
         if dev.type != "cuda":
             raise ValueError(f"device={dev}: this MPPI runs its hot path on MI355X only; there is no CPU path "
@@ -359,6 +375,8 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                          f(self._sigma_max))
         if self._action_cost:  # mppi.py:294-316,330-336
             self._h.call("mppi_set_action_cost", 1, self._action_cost_weight)
+        if self._noise_beta.any():  # (all zero: the default draw, no call into the library)
+            self._h.call("mppi_set_noise_correlation", self._noise_beta.ctypes.data_as(C.c_void_p))
         # the LBPS search and the MPO step run inside the library (no interpreter work per probe) whenever the
         # statistics come from this device alone; sharded solvers combine the shards' statistics in Python
         self._search_in_library = auto_lambda_stats == "device" and self._world == 1
@@ -673,6 +691,20 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         if self._adapt_covariance:  # the adapted table goes back to the constructor's `sigmas`
             self._sigma_seq_reset = self._sigmas.repeat(self._horizon, 1).contiguous()  # (alive until the copy ran)
             self._h.call("mppi_set_sigma_table", _ptr(self._sigma_seq_reset), 1, self._stream())
+
+    @property
+    def noise_beta(self) -> torch.Tensor:
+        """The lag-1 correlation of the sampling noise along the horizon, [dim_control] (a copy; zeros: independent steps)."""
+        return torch.from_numpy(self._noise_beta.copy())
+
+    def set_noise_beta(self, beta) -> None:
+        """Change `noise_beta` between solves (same values and errors as the constructor argument; 0 switches the filter off
+        and the next solve draws the default solver's noise).  Set-up path: synchronises.  deepcopy and state_dict() carry it."""
+        b = _host.check_noise_beta_args(beta, self._dim_control, self._noise_source, self._action_cost)
+        if b.any() or self._noise_beta.any():
+            self._h.call("mppi_set_noise_correlation", b.ctypes.data_as(C.c_void_p))
+        self._noise_beta = b
+        self._ctor["noise_beta"] = torch.from_numpy(b.copy())
 
     @property
     def sigma_seq(self) -> torch.Tensor:
