@@ -59,7 +59,9 @@ enum {
     MPPI_MODEL_NAV2D = 3,       /* src/envs/navigation_2d.py:218-279                          */
     MPPI_MODEL_RACING = 4,      /* src/envs/racing_env.py:327-372 + example/racing.py:110-159 */
     MPPI_MODEL_MJCARTPOLE = 5,  /* example/mujoco_cartpole.py:20-81 (continuous force, masspole = 1) */
-    MPPI_MODEL_GOALZONE = 6     /* src/envs/goal_in_danger_zone.py:113-156 (7-state unicycle + circle) */
+    MPPI_MODEL_GOALZONE = 6,    /* src/envs/goal_in_danger_zone.py:113-156 (7-state unicycle + circle) */
+    MPPI_MODEL_MLP41 = 7,       /* learned dynamics: a small MLP, 4 states, 1 control (mppi_set_mlp)  */
+    MPPI_MODEL_MLP42 = 8        /* the same with 2 controls                                           */
 };
 
 /* Racing parameter vector (mppi_set_model_params), racing_env.py:37-42,341-370, racing.py:41-46 */
@@ -73,6 +75,13 @@ enum { MPPI_NP_VMIN = 0, MPPI_NP_VMAX, MPPI_NP_WMIN, MPPI_NP_WMAX, MPPI_NP_DT, M
 /* Goal-in-danger-zone parameter vector, goal_in_danger_zone.py:78-87,113-156 */
 enum { MPPI_GP_VMIN = 0, MPPI_GP_VMAX, MPPI_GP_WMIN, MPPI_GP_WMAX, MPPI_GP_DT, MPPI_GP_GX, MPPI_GP_GY, MPPI_GP_CX,
        MPPI_GP_CY, MPPI_GP_RADIUS, MPPI_GP_PENALTY, MPPI_GP_COUNT };
+
+/* Learned-dynamics (MLP) cost parameters: c = sum_m q[m] * (s[m] - g[m])^2 + sum_k r[k] * u[k]^2 (mppi_set_mlp has the
+ * arithmetic): g[4], q[4], r[dim_control] -> 9 values for MPPI_MODEL_MLP41, 10 for MPPI_MODEL_MLP42 */
+enum { MPPI_MP_G = 0, MPPI_MP_Q = 4, MPPI_MP_R = 8, MPPI_MP_COUNT41 = 9, MPPI_MP_COUNT42 = 10 };
+#define MPPI_MLP_HIDDEN 32 /* hidden width of the table; narrower layers are zero-padded by the caller */
+/* mppi_set_mlp `activation` */
+enum { MPPI_MLP_RELU = 0, MPPI_MLP_TANH = 1 };
 
 #define MPPI_MAX_PARAMS 32
 #define MPPI_MAX_DIM_STATE 8
@@ -101,7 +110,7 @@ typedef struct MppiConfig {
 const char* mppi_version(void);
 /* Integer version of THIS header's function signatures; bindings compare it with the constant they were written
  * against and refuse a stale library (a changed argument list would otherwise be called with shifted arguments). */
-#define MPPI_ABI_VERSION 13
+#define MPPI_ABI_VERSION 14
 int mppi_abi_version(void);
 /* Number of visible HIP devices (0 => the product cannot run; callers must fail loudly). */
 int mppi_device_count(void);
@@ -159,6 +168,29 @@ int mppi_download_map(mppi_handle_t h, int slot, uint8_t* cells_host, int* nx, i
 /* racing_controller.reference_path = calc_ref_trajectory(...) (example/racing.py:73-81):
  * ref [rows][4] = (x, y, yaw, v_target), rows >= T (the cost reads rows 0..T-1). */
 int mppi_set_reference(mppi_handle_t h, const float* ref_host, int rows, void* stream);
+/* Learned dynamics for MPPI_MODEL_MLP41 / MPPI_MODEL_MLP42: the weights of a multi-layer perceptron with 4 states,
+ * dc = 1 / 2 controls, `hidden_layers` = 1 or 2 hidden layers of MPPI_MLP_HIDDEN = 32 units and 4 outputs, as ONE table of
+ * n_floats = 32*IN + 32 + 32*32 + 32 + 4*32 + 4 fp32 values (IN = 4 + dc: 1380 / 1412), row-major, in the order
+ *     W1[32][IN], b1[32], W2[32][32], b2[32], W3[4][32], b3[4]
+ * (W2 / b2 are not read with one hidden layer).  A narrower layer is padded with zero rows, columns and biases, a model
+ * with fewer than four states with components that stay zero: relu(0) = tanh(0) = 0 and adding w*0 or 0*x changes no bit
+ * of a sum.  The step, in fp32 — at option "math" = 0 every operation rounds on its own, in exactly this order; the fast
+ * levels may contract a*b + c and evaluate tanh with the hardware exponential and reciprocal:
+ *     x = [s[0..3], u[0..dc-1]]                    (u: the solver-clamped action; the model does not clamp again)
+ *     z[j] = b1[j]; for i = 0..IN-1: z[j] = z[j] + W1[j][i] * x[i];   h1[j] = act(z[j])             (j = 0..31)
+ *     two hidden layers: the same over the 32 entries of h1 with W2, b2 -> h2
+ *     o[m] = b3[m]; for j = 0..31: o[m] = o[m] + W3[m][j] * h[j]                                    (m = 0..3)
+ *     next[m] = residual ? s[m] + o[m] : o[m]
+ * act = fmaxf(z, 0) (MPPI_MLP_RELU) or tanh (MPPI_MLP_TANH).  Stage cost on the state a step starts from and its action,
+ * terminal cost the same function of the last state with a zero action (parameters: MPPI_MP_*, mppi_set_model_params):
+ *     c = 0; for m = 0..3: d = s[m] - g[m], c = c + q[m] * (d * d); for k = 0..dc-1: c = c + r[k] * (u[k] * u[k])
+ * The table is staged and copied on `stream` (no host wait), like mppi_set_reference's window, and may be replaced between
+ * solves (a model learned online: every tick); a lazily completed state sequence is completed with the old weights first.
+ * MPPI_E_INVALID for another model's handle, a wrong count, a flag out of range or a value that is not finite.  Solves on
+ * an MLP handle without a table return MPPI_E_STATE.  mppi_clone_state copies table and flags; mppi_model_step does not
+ * take these models (MPPI_E_INVALID: it has no handle to take the table from). */
+int mppi_set_mlp(mppi_handle_t h, const float* table_host, int n_floats, int hidden_layers, int activation, int residual,
+                 void* stream);
 
 /* The racing control tick without the host (example/racing.py:73-81,161-218,221-266).
  *   mppi_set_center_path  `env.racing_center_path` [n][3] = (x, y, yaw) and the constants of

@@ -15,15 +15,18 @@ LIB_PATH = os.environ.get("MPPI_HIP_LIB") or os.path.join(_HERE, "csrc", "libmpp
 MODEL_GENERIC = -1
 MAX_DIM_CONTROL = 4           # controls held by MppiConfig
 MAX_DIM_CONTROL_GENERIC = 64  # opaque callables: any dim_control up to this
-MODEL_IDS = {"pendulum": 0, "cartpole": 1, "mountaincar": 2, "nav2d": 3, "racing": 4, "mjcartpole": 5, "goalzone": 6}
+MODEL_IDS = {"pendulum": 0, "cartpole": 1, "mountaincar": 2, "nav2d": 3, "racing": 4, "mjcartpole": 5, "goalzone": 6,
+             "mlp41": 7, "mlp42": 8}
 MODEL_DIMS = {"pendulum": (2, 1), "cartpole": (4, 1), "mountaincar": (2, 1), "nav2d": (3, 2), "racing": (4, 2),
-              "mjcartpole": (4, 1), "goalzone": (7, 2)}
+              "mjcartpole": (4, 1), "goalzone": (7, 2), "mlp41": (4, 1), "mlp42": (4, 2)}
+MLP_HIDDEN = 32               # MPPI_MLP_HIDDEN
+MLP_ACTIVATIONS = {"relu": 0, "tanh": 1}  # MPPI_MLP_*
 SUMMARY_HEAD = 4
 LAMBDA_DEVICE = -1.0  # MPPI_LAMBDA_DEVICE: "the temperature a device-resident rule left on the device"
 AUTO_RULES = {None: 0, "ESSPS": 1, "LBPS": 2, "MPO": 3}  # MPPI_AUTO_*
 
 # every symbol include/mppi_hip.h declares
-ABI_VERSION = 13  # MPPI_ABI_VERSION of the header this binding was written against
+ABI_VERSION = 14  # MPPI_ABI_VERSION of the header this binding was written against
 
 SYMBOLS = [
     "mppi_version", "mppi_abi_version", "mppi_device_count", "mppi_last_error", "mppi_create", "mppi_destroy", "mppi_set_control_limits",
@@ -39,6 +42,7 @@ SYMBOLS = [
     "mppi_set_covariance_adaptation", "mppi_update_covariance", "mppi_get_sigma_table", "mppi_set_sigma_table",
     "mppi_set_action_cost", "mppi_set_action_cost_lambda", "mppi_add_action_cost",
     "mppi_set_noise_correlation", "mppi_get_noise_correlation",
+    "mppi_set_mlp",
 ]
 
 
@@ -160,6 +164,7 @@ def load():
     lib.mppi_add_action_cost.argtypes = [vp, f32, vp]
     lib.mppi_set_noise_correlation.argtypes = [vp, vp]
     lib.mppi_get_noise_correlation.argtypes = [vp, vp]
+    lib.mppi_set_mlp.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the .so does not export what the header declares
         if name not in ("mppi_version", "mppi_last_error"):

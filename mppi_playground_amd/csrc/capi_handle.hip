@@ -243,7 +243,7 @@ int mppi_destroy(mppi_handle_t h) {
 // copy.deepcopy(solver) (the reference is a plain nn.Module, mppi.py:16: every tensor it holds is copied with it): make `dst`
 // — a handle created from the same MppiConfig — continue exactly like `src` from here: warm start, noise identity, costs and
 // minimum of the last solve (queries), Savitzky-Golay history, the temperature and every device-resident search / dual
-// state, model parameters, maps, reference window and path index, options.  Not copied: the single-launch solve's, the Brent
+// state, model parameters, maps, reference window and path index, the weight table of a learned model, options.  Not copied: the single-launch solve's, the Brent
 // search's, the ESSPS round-1 and the exchange's tags and buffers, the timers.  Set-up path: synchronises the device.
 int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
     if (!dst || !src || dst == src) return fail(dst, MPPI_E_INVALID, "clone_state: two distinct handles");
@@ -335,6 +335,11 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
         if (int rc = reserve_ref(dst, (int)(sm.ref.n / 8))) return rc;
         if (int rc = clone_buf(dst, dm.ref.p, sm.ref.p, sm.ref.n)) return rc;
         if (sm.ctx.ref) { dm.ctx.ref = dm.ref; dm.ctx.ref_rows = sm.ctx.ref_rows; }
+    }
+    if (sm.mlp && sm.ctx.ref) {  // learned dynamics: the weight table, with the flags that ride in ref_rows
+        if (dm.mlp.n != sm.mlp.n) HIP_TRY(dst, dm.mlp.alloc(sm.mlp.n));
+        CLONE(model.mlp);
+        dm.ctx.ref = dm.mlp; dm.ctx.ref_rows = sm.ctx.ref_rows;
     }
     if (sm.center_n) {
         HIP_TRY(dst, dm.center8.alloc(sm.center8.n));

@@ -1,5 +1,7 @@
 // capi_model.hip — C ABI (include/mppi_hip.h): model parameters, maps, the reference and its device-resident window,
 // env.step and grid lookups on the device.
+#include <cmath>
+
 #include "mppi_handle.hpp"
 #include "mppi_env.hpp"
 #include "mppi_maps.hpp"
@@ -172,6 +174,7 @@ int mppi_download_map(mppi_handle_t h, int slot, uint8_t* cells_host, int* nx, i
 
 int mppi_set_reference(mppi_handle_t h, const float* ref, int rows, void* stream) {
     if (!h || !ref || rows < 1) return fail(h, MPPI_E_INVALID, "bad reference");
+    if (is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "a learned-dynamics handle has no reference window");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = reserve_ref(h, rows)) return rc;
     float* st = nullptr; hipEvent_t ev = nullptr;
@@ -186,6 +189,30 @@ int mppi_set_reference(mppi_handle_t h, const float* ref, int rows, void* stream
     HIP_TRY(h, hipEventRecord(ev, s));
     h->model.ctx.ref = h->model.ref;
     h->model.ctx.ref_rows = rows;
+    return MPPI_OK;
+}
+
+int mppi_set_mlp(mppi_handle_t h, const float* table, int n_floats, int hidden_layers, int activation, int residual,
+                 void* stream) {
+    if (!h || !table) return fail(h, MPPI_E_INVALID, "bad weight table");
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the weight table belongs to the learned-dynamics models");
+    if (n_floats != mlp_table_floats(h->dc)) return fail(h, MPPI_E_INVALID, "weight table: wrong number of values for this model");
+    if (hidden_layers < 1 || hidden_layers > 2 || (activation != MPPI_MLP_RELU && activation != MPPI_MLP_TANH) ||
+        (residual != 0 && residual != 1))
+        return fail(h, MPPI_E_INVALID, "weight table: hidden_layers 1 or 2, activation relu or tanh, residual 0 or 1");
+    for (int i = 0; i < n_floats; ++i)
+        if (!std::isfinite(table[i])) return fail(h, MPPI_E_INVALID, "weight table: every value must be finite");
+    if (int rc = settle_state_seq(h)) return rc;  // a lazily completed state sequence belongs to the OLD weights: roll it out first
+    hipStream_t s = (hipStream_t)stream;
+    if (!h->model.mlp) HIP_TRY(h, h->model.mlp.alloc((size_t)n_floats));
+    float* st = nullptr; hipEvent_t ev = nullptr;
+    if (int rc = stage_slot(h, (size_t)n_floats, &st, &ev)) return rc;
+    std::memcpy(st, table, sizeof(float) * (size_t)n_floats);
+    HIP_TRY(h, hipMemcpyAsync(h->model.mlp, st, sizeof(float) * (size_t)n_floats, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(ev, s));
+    h->model.ctx.ref = h->model.mlp;
+    h->model.ctx.ref_rows = (hidden_layers == 2 ? MLP_TWO_LAYERS : 0) | (activation == MPPI_MLP_TANH ? MLP_TANH : 0) |
+                            (residual ? MLP_RESIDUAL : 0);
     return MPPI_OK;
 }
 
@@ -244,6 +271,7 @@ int mppi_get_path_index(mppi_handle_t h, int32_t* cind_out_host, void* stream) {
 
 int mppi_get_reference(mppi_handle_t h, float* ref_out, int rows, int on_device, void* stream) {
     if (!h || !ref_out || rows < 1) return fail(h, MPPI_E_INVALID, "bad get_reference arguments");
+    if (is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "a learned-dynamics handle has no reference window");
     if (!h->model.ctx.ref || rows > h->model.ctx.ref_rows) return fail(h, MPPI_E_STATE, "no reference window of that many rows");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipMemcpy2DAsync(ref_out, 4 * sizeof(float), h->model.ref, 8 * sizeof(float), 4 * sizeof(float), (size_t)rows,
@@ -256,6 +284,7 @@ int mppi_model_step(int model, const float* params_host, int n_params, const flo
                     const float* state_dev, const float* action_dev, float* next_state_dev, const float* goal_xy_host,
                     float goal_threshold, uint8_t* reached_out_dev, void* stream) {
     ModelDims md{};
+    if (is_mlp(model)) return MPPI_E_INVALID;  // (no handle: nowhere to take the weight table from)
     if (!model_dims(model, md) || n_params < 0 || n_params > MPPI_MAX_PARAMS || (n_params && !params_host) ||
         !state_dev || !action_dev || !next_state_dev || (reached_out_dev && !goal_xy_host) || md.dc > MPPI_MAX_DIM_CONTROL)
         return MPPI_E_INVALID;

@@ -121,6 +121,36 @@ __device__ __forceinline__ bool rollout_states_noise(const float* __restrict__ x
 #pragma unroll
         for (int j2 = 0; j2 < DS; ++j2) { out[t * DS + j2] = ss[j2]; s[j2] = sn[j2]; }
     };
+    // The learned-dynamics models' step is some 4 KB of code (mppi_models.inc): their row is walked by ONE rolled loop over the
+    // steps — a group is fetched where its first step runs, the step's inputs are picked with selects on the wave-uniform
+    // position in the group — so that this walk holds one copy of the step instead of 4 / DC + 1 (see trajectory_cost).
+    // Same operations per step, same order, same bits; the re-roll gives up the look-ahead of the noise chain.
+    if constexpr (MODEL == MPPI_MODEL_MLP41 || MODEL == MPPI_MODEL_MLP42) {
+        auto pick4 = [](float a0, float a1, float a2, float a3, int i) {
+            float r = a0;
+            r = i == 1 ? a1 : r;
+            r = i == 2 ? a2 : r;
+            r = i == 3 ? a3 : r;
+            return r;
+        };
+        float4 cur = loadg(0), m = mp[0];
+#pragma clang loop unroll(disable)
+        for (int t = 0; t < T; ++t) {
+            const int g = t / SPG, j = t - g * SPG;
+            if (j == 0 && g > 0) { cur = loadg(g); m = mp[g]; }
+            float u[DC], sn[DS], ss[DS];
+#pragma unroll
+            for (int kk = 0; kk < DC; ++kk)
+                u[kk] = clampf(pick4(m.x, m.y, m.z, m.w, j * DC + kk) + pick4(cur.x, cur.y, cur.z, cur.w, j * DC + kk),
+                               d.u_min[kk], d.u_max[kk]);
+            M::step(ctx, s, u, sn, ss, bad);
+#pragma unroll
+            for (int j2 = 0; j2 < DS; ++j2) { out[t * DS + j2] = ss[j2]; s[j2] = sn[j2]; }
+        }
+#pragma unroll
+        for (int j = 0; j < DS; ++j) out[T * DS + j] = s[j];
+        return bad;
+    }
     float4 nxt = loadg(0);
     const int gfull = T / SPG;  // groups whose SPG steps all exist
     for (int g = 0; g < gfull; ++g) {

@@ -280,6 +280,7 @@ struct MppiSolver {
         DevBuf<uint8_t> map_cells[2];
         DevBuf<uint8_t> map_pad;       // padded (and, for racing, summed) grid of the FAST lookup
         DevBuf<float> ref;             // [rows][8] reference window
+        DevBuf<float> mlp;             // weight table of the learned-dynamics models (mppi_set_mlp); ctx.ref points at it
         // device-resident reference window (mppi_set_center_path / mppi_ref_window)
         DevBuf<float> center8;         // [n][8] centre line with sin/cos of the yaw
         DevBuf<int32_t> win_dind;      // [rows] index offsets of the window rows
@@ -353,14 +354,18 @@ inline bool model_dims(int model, ModelDims& md) {
     case MPPI_MODEL_RACING: md = {4, 2}; return true;
     case MPPI_MODEL_MJCARTPOLE: md = {4, 1}; return true;
     case MPPI_MODEL_GOALZONE: md = {7, 2}; return true;
+    case MPPI_MODEL_MLP41: md = {4, 1}; return true;
+    case MPPI_MODEL_MLP42: md = {4, 2}; return true;
     }
     return false;
 }
 // parameters the dynamics of `model` read (the models without any take none)
 inline int model_param_count(int model) {
     return model == MPPI_MODEL_RACING ? MPPI_RP_COUNT : model == MPPI_MODEL_NAV2D ? MPPI_NP_COUNT
-           : model == MPPI_MODEL_GOALZONE ? MPPI_GP_COUNT : 0;
+           : model == MPPI_MODEL_GOALZONE ? MPPI_GP_COUNT : model == MPPI_MODEL_MLP41 ? MPPI_MP_COUNT41
+           : model == MPPI_MODEL_MLP42 ? MPPI_MP_COUNT42 : 0;
 }
+inline bool is_mlp(int model) { return model == MPPI_MODEL_MLP41 || model == MPPI_MODEL_MLP42; }
 
 // Times one stage with a pair of HIP events (no host synchronisation); pairs accumulate until mppi_get_timing() drains
 // them.  The events ride on the stage's own dispatches (hipExtLaunchKernel): the start event on its first kernel launch,
@@ -472,6 +477,8 @@ inline int math_level(mppi_handle_t h) { return use_fast(h) ? (h->opt.math_fast 
         MPPI_DISPATCH_HW(MPPI_MODEL_RACING, CALL)                                                     \
         MPPI_DISPATCH_NOHW(MPPI_MODEL_MJCARTPOLE, CALL)                                               \
         MPPI_DISPATCH_HW(MPPI_MODEL_GOALZONE, CALL)                                                   \
+        MPPI_DISPATCH_NOHW(MPPI_MODEL_MLP41, CALL)                                                    \
+        MPPI_DISPATCH_NOHW(MPPI_MODEL_MLP42, CALL)                                                    \
         }                                                                                             \
     } while (0)
 
@@ -484,6 +491,7 @@ inline int check_ready(mppi_handle_t h) {
     if (m == MPPI_MODEL_RACING && !h->model.map_cells[1]) return fail(h, MPPI_E_STATE, "lane map (slot 1) not uploaded");
     if (m == MPPI_MODEL_RACING && (!h->model.ctx.ref || h->model.ctx.ref_rows < h->d.T))
         return fail(h, MPPI_E_STATE, "reference path not set or shorter than the horizon");
+    if (is_mlp(m) && !h->model.ctx.ref) return fail(h, MPPI_E_STATE, "no weight table: call mppi_set_mlp first");
     return MPPI_OK;
 }
 

@@ -55,6 +55,14 @@ struct ModelCtx {
     int32_t wrap_safe;     // per-step heading increments are < pi: wrapped angles stay in the narrow range
 };
 
+// The learned-dynamics models (MPPI_MODEL_MLP41 / MLP42; mppi_set_mlp): the weight table is ModelCtx::ref and the
+// launch-uniform flags ride in ModelCtx::ref_rows, two fields these models have no other use for, so the kernels'
+// argument struct is what it was.
+constexpr int MLP_TWO_LAYERS = 1, MLP_TANH = 2, MLP_RESIDUAL = 4;
+constexpr int mlp_table_floats(int dc) {
+    return MPPI_MLP_HIDDEN * (4 + dc) + MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN * MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN + 4 * MPPI_MLP_HIDDEN + 4;
+}
+
 // Host-side plan of the padded grid.  The models clamp positions to [xlo, xhi] x [ylo, yhi]; if every index
 // round(p/cell + origin) reachable under that clamp lies in [0, nx] x [0, ny], the lookup needs no bounds test.
 // koff = the constant (mod 2^32) that occ_lookup_pad's index carries; returns false when the plan does not apply.

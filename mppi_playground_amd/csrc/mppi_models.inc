@@ -594,5 +594,113 @@ struct Model<MPPI_MODEL_RACING, FAST> {  // src/envs/racing_env.py:327-372, exam
     }
 };
 
+// Learned dynamics: a multi-layer perceptron whose weights are data (include/mppi_hip.h, mppi_set_mlp, states the
+// arithmetic; the table is ctx.ref, the flags ctx.ref_rows).  Every product-sum is written a * b + c: mppi::strict rounds
+// each operation on its own (the numpy restatement of tests/mlp_ref.py, bit for bit with relu), the fast namespaces may
+// contract.  The weights are wave-uniform: they are read at uniform addresses and arrive as the scalar operand of the VALU
+// multiply-adds.  Shape of the code (the step is inlined once per step of a float4 group, per drain half, in the epilogue
+// and per noise mode, so the network is NOT unrolled as a whole):
+//   two hidden layers: layer 1 unrolled over its 32 units (h1 lives in 32 statically indexed registers), then ONE rolled
+//     loop over j that forms h2[j] from h1, applies the activation and adds W3[m][j] * h2[j] into the four outputs;
+//   one hidden layer:  one rolled loop over j that forms h1[j] from the IN inputs and adds W3[m][j] * h1[j].
+// Both visit every sum in ascending index order.  tanh at the fast levels: 1 - 2 / (e^(2z) + 1) with the hardware
+// exponential and reciprocal (e = inf and e = 0 give +-1: no validity range, `bad` is never raised).
+template <bool FAST>
+MPPI_HD float mlp_act(float z, bool use_tanh) {
+    if (!use_tanh) return fmaxf(z, 0.0f);
+    if (FAST) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const float e = __builtin_amdgcn_exp2f(z * 2.88539008f);  // 2 * log2(e)
+        return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
+#else
+        return 1.0f - 2.0f / (expf(2.0f * z) + 1.0f);
+#endif
+    }
+    return tanhf(z);
+}
+
+// The table as the step reads it.  On the device the pointer is cast into the constant address space: the table is not written
+// while a kernel runs and every address is wave-uniform, so each read is a scalar load (a plain global pointer the compiler
+// cannot prove unclobbered next to the kernels' stores is read with per-lane vector loads: 64 copies of one value in VGPRs).
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const float __attribute__((address_space(4)))* MlpTable;
+#else
+typedef const float* MlpTable;
+#endif
+
+template <int DCN, bool FAST>
+struct MlpModel {
+    using K = NoStepConst;
+    static constexpr int KROW = 0;
+    static MPPI_HD K load_k(const float*, int) { return K{}; }
+    static MPPI_HD void check_state(const ModelCtx&, const float*, bool&) {}
+    static MPPI_HD void enter(float*) {}
+    static constexpr int DS = 4, DC = DCN, IN = DS + DC, H = MPPI_MLP_HIDDEN;
+    // offsets into the table: W1[H][IN], b1[H], W2[H][H], b2[H], W3[DS][H], b3[DS]
+    static constexpr int OB1 = H * IN, OW2 = OB1 + H, OB2 = OW2 + H * H, OW3 = OB2 + H, OB3 = OW3 + DS * H;
+    static MPPI_HD void step(const ModelCtx& c, const float* s, const float* u, float* sn, float* ss, bool&, bool = false, bool = false) {
+        const MlpTable W = (MlpTable)c.ref;
+        const bool use_tanh = (c.ref_rows & MLP_TANH) != 0;
+        float x[IN], o[DS];
+#pragma unroll
+        for (int m = 0; m < DS; ++m) { x[m] = s[m]; o[m] = W[OB3 + m]; }
+#pragma unroll
+        for (int k = 0; k < DC; ++k) x[DS + k] = u[k];
+        if (c.ref_rows & MLP_TWO_LAYERS) {
+            float h1[H];
+#pragma unroll
+            for (int j = 0; j < H; ++j) {
+                float z = W[OB1 + j];
+#pragma unroll
+                for (int i = 0; i < IN; ++i) z = z + W[j * IN + i] * x[i];
+                h1[j] = mlp_act<FAST>(z, use_tanh);
+            }
+#pragma clang loop unroll(disable)
+            for (int j = 0; j < H; ++j) {
+                const MlpTable w2 = W + OW2 + j * H;
+                float z = W[OB2 + j];
+#pragma unroll
+                for (int i = 0; i < H; ++i) z = z + w2[i] * h1[i];
+                const float h = mlp_act<FAST>(z, use_tanh);
+#pragma unroll
+                for (int m = 0; m < DS; ++m) o[m] = o[m] + W[OW3 + m * H + j] * h;
+            }
+        } else {
+#pragma clang loop unroll(disable)
+            for (int j = 0; j < H; ++j) {
+                const MlpTable w1 = W + j * IN;
+                float z = W[OB1 + j];
+#pragma unroll
+                for (int i = 0; i < IN; ++i) z = z + w1[i] * x[i];
+                const float h = mlp_act<FAST>(z, use_tanh);
+#pragma unroll
+                for (int m = 0; m < DS; ++m) o[m] = o[m] + W[OW3 + m * H + j] * h;
+            }
+        }
+        const bool residual = (c.ref_rows & MLP_RESIDUAL) != 0;
+#pragma unroll
+        for (int m = 0; m < DS; ++m) {
+            ss[m] = s[m];
+            sn[m] = residual ? s[m] + o[m] : o[m];
+        }
+    }
+    static MPPI_HD float cost(const ModelCtx& c, const K&, const float* s, const float* u, const float*, bool&) {
+        const float* P = c.P;
+        float a = 0.0f;
+#pragma unroll
+        for (int m = 0; m < DS; ++m) {
+            const float d = s[m] - P[MPPI_MP_G + m];
+            a = a + P[MPPI_MP_Q + m] * (d * d);
+        }
+#pragma unroll
+        for (int k = 0; k < DC; ++k) a = a + P[MPPI_MP_R + k] * (u[k] * u[k]);
+        return a;
+    }
+};
+template <bool FAST>
+struct Model<MPPI_MODEL_MLP41, FAST> : MlpModel<1, FAST> {};
+template <bool FAST>
+struct Model<MPPI_MODEL_MLP42, FAST> : MlpModel<2, FAST> {};
+
 }  // namespace MPPI_MODEL_NS
 }  // namespace mppi

@@ -131,6 +131,33 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
         for (int j = 0; j < DS; ++j) s[j] = sn[j];
         ++t;
     };
+    // The learned-dynamics models' step is some 4 KB of code (a layer of 32 units and its activations, unrolled: mppi_models.inc),
+    // and every unrolled step of a float4 group below is a copy of it: 4 / DC steps x {two drain halves, epilogue} would be twelve
+    // copies, most of the instruction cache.  Their groups are walked by a ROLLED loop instead: the step's inputs are picked
+    // from the group's registers with selects on the (wave-uniform) step index — three per value, against ~1300 multiply-adds
+    // per step — and each of the three walks holds one copy.  Same operations per step in the same order.
+    constexpr bool ROLL_GROUP = MODEL == MPPI_MODEL_MLP41 || MODEL == MPPI_MODEL_MLP42;
+    auto pick4 = [](float a0, float a1, float a2, float a3, int i) {  // (scalars: nothing here can be turned into an indexed load)
+        float r = a0;
+        r = i == 1 ? a1 : r;
+        r = i == 2 ? a2 : r;
+        r = i == 3 ? a3 : r;
+        return r;
+    };
+    auto rolled_group = [&](const float4 ev, const float4 mv, const float4 gv, bool ragged) {
+#pragma clang loop unroll(disable)
+        for (int g = 0; g < SPG; ++g) {
+            if (ragged && !(t < d.T)) break;
+            float e1[DC], m1[DC], g1[DC];
+#pragma unroll
+            for (int k = 0; k < DC; ++k) {
+                e1[k] = pick4(ev.x, ev.y, ev.z, ev.w, g * DC + k);
+                m1[k] = pick4(mv.x, mv.y, mv.z, mv.w, g * DC + k);
+                g1[k] = AC ? pick4(gv.x, gv.y, gv.z, gv.w, g * DC + k) : 0.0f;
+            }
+            one_step(e1, m1, g1);
+        }
+    };
     // Groups walked by the loops below: SPG steps each, no per-step bound checks.  Tiles: every group that lies completely
     // inside the horizon, d.T / SPG.  Regenerating loop: only the groups that still have a SUCCESSOR to generate,
     // (d.T - 1) / SPG.  An iteration of that loop generates the noise of the next group, a whole Philox4x32-10 and two
@@ -172,8 +199,12 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
                 const float mv[4] = {m4.x, m4.y, m4.z, m4.w};
                 float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                 if constexpr (AC) { const float4 gq = g4[r]; gv[0] = gq.x; gv[1] = gq.y; gv[2] = gq.z; gv[3] = gq.w; }
+                if constexpr (ROLL_GROUP) {
+                    rolled_group(e, m4, AC ? g4[r] : float4{0.0f, 0.0f, 0.0f, 0.0f}, false);
+                } else {
 #pragma unroll
-                for (int g = 0; g < SPG; ++g) one_step(ev + g * DC, mv + g * DC, gv + g * DC);
+                    for (int g = 0; g < SPG; ++g) one_step(ev + g * DC, mv + g * DC, gv + g * DC);
+                }
                 e = en;
                 m4 = m4n;
             }
@@ -190,8 +221,12 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
             const float mv[4] = {m4.x, m4.y, m4.z, m4.w};
             float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             if constexpr (AC) { const float4 gq = g4[r]; gv[0] = gq.x; gv[1] = gq.y; gv[2] = gq.z; gv[3] = gq.w; }
+            if constexpr (ROLL_GROUP) {
+                rolled_group(e, m4, AC ? g4[r] : float4{0.0f, 0.0f, 0.0f, 0.0f}, false);
+            } else {
 #pragma unroll
-            for (int g = 0; g < SPG; ++g) one_step(ev + g * DC, mv + g * DC, gv + g * DC);
+                for (int g = 0; g < SPG; ++g) one_step(ev + g * DC, mv + g * DC, gv + g * DC);
+            }
             e = e1;
             m4 = m4n;
             const float4* nptr = np + (int64_t)min(r + 2, d.R - 1) * 64;
@@ -207,9 +242,13 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
             const float4 gq = g4[t / SPG];
             gv[0] = gq.x; gv[1] = gq.y; gv[2] = gq.z; gv[3] = gq.w;
         }
+        if constexpr (ROLL_GROUP) {
+            rolled_group(e, m4, AC ? g4[t / SPG] : float4{0.0f, 0.0f, 0.0f, 0.0f}, true);
+        } else {
 #pragma unroll
-        for (int g = 0; g < SPG; ++g)
-            if (t < d.T) one_step(ev + g * DC, mv + g * DC, gv + g * DC);
+            for (int g = 0; g < SPG; ++g)
+                if (t < d.T) one_step(ev + g * DC, mv + g * DC, gv + g * DC);
+        }
     }
     // terminal cost: zero action, stale prev_action U[:, max(T-2,0)] and stale t = T-1
     // (mppi.py:318-328); knext already holds the constants of row T-1

@@ -5,3 +5,5 @@ cost(state[B,ds], action[B,dc], info) -> [B] in torch — and additionally carri
 (pi_mpc/native.py) so that pi_mpc.mppi.MPPI runs it fused on the device.  Rendering / video /
 gymnasium simulators of the reference are UI and out of scope; `render()`/`close()` are no-ops.
 """
+
+from envs.mlp_model import MLPModel  # noqa: E402,F401  (learned dynamics: an MLP whose weights are data)

@@ -1,0 +1,208 @@
+"""Learned dynamics as an MPPI plugin: a small multi-layer perceptron fitted to data, with a quadratic cost.
+
+    model = MLPModel.from_module(net, goal=[...], q=[...], r=[...])      # net: nn.Sequential of Linear / ReLU / Tanh
+    solver = MPPI(dim_state=4, dim_control=dc, dynamics=model.dynamics, cost_func=model.cost, ...)
+
+`dynamics` and `cost` are plain torch code — they run anywhere, the solver's generic path included — and carry the native
+tag "mlp41" / "mlp42" (by the control width), so that pi_mpc.mppi.MPPI runs them fused on the device: the weights are data
+(one table, include/mppi_hip.h: mppi_set_mlp), the functor that evaluates them is one more native model.
+
+What the device path takes: a state of 4 components, 1 or 2 controls, one or two hidden layers of at most 32 units, relu or
+tanh.  Narrower layers and a narrower state are zero-padded here (rows, columns and biases: relu(0) = tanh(0) = 0 and adding
+w * 0 changes no bit of a sum); the CALLER pads the state vector it hands to the solver with components that stay zero.
+
+The arithmetic, in fp32 and in this order (the torch code below, the device functor and tests/mlp_ref.py state the same):
+    x = [s[0..3], u[0..dc-1]]          (u: the solver-clamped action, not clamped again)
+    z[j] = b1[j]; for i ascending: z[j] = z[j] + W1[j][i] * x[i];  h1[j] = act(z[j])
+    (second hidden layer: the same over h1)
+    o[m] = b3[m]; for j ascending: o[m] = o[m] + W3[m][j] * h[j]
+    next[m] = s[m] + o[m] if residual else o[m]
+    cost = sum_m q[m] * (s[m] - goal[m])^2 + sum_k r[k] * u[k]^2      (terminal: the same with u = 0)
+"""
+from __future__ import annotations
+
+from typing import Sequence
+
+import numpy as np
+import torch
+
+from pi_mpc.native import native_model
+
+DS = 4       # state components of the native models
+HIDDEN = 32  # hidden width of the device table (MPPI_MLP_HIDDEN)
+
+
+def _f32(a) -> np.ndarray:
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    return np.array(a, dtype=np.float32)
+
+
+def _provider(owner):
+    return owner.native_inputs()
+
+
+class MLPModel:
+    def __init__(self, weights: Sequence, biases: Sequence, activation: str = "tanh", residual: bool = True, goal=None,
+                 q=None, r=None):
+        """weights / biases: per layer, torch.nn.Linear's layout — W1 [h1, ds + dc], (W2 [h2, h1],) W3 [ds, h] with
+        ds <= 4 state components, dc = 1 or 2 controls and h1, h2 <= 32.  goal, q: [ds] (defaults 0 / 1), r: [dc] (default 0).
+        ValueError for anything the device path does not take."""
+        if activation not in ("relu", "tanh"):
+            raise ValueError("activation must be 'relu' or 'tanh'")
+        self.activation = activation
+        self.residual = bool(residual)
+        self.version = 0
+        self._set(weights, biases)
+        ds, dc = self.dim_state_model, self.dim_control
+
+        def vec(v, n, default, name):
+            a = np.full(n, default, np.float32) if v is None else _f32(v).reshape(-1)
+            if a.shape != (n,) or not np.all(np.isfinite(a)):
+                raise ValueError(f"{name} must hold {n} finite values")
+            return a
+
+        goal4, q4 = np.zeros(DS, np.float32), np.zeros(DS, np.float32)
+        goal4[:ds] = vec(goal, ds, 0.0, "goal")
+        q4[:ds] = vec(q, ds, 1.0, "q")
+        # (read-only: the torch callables and the device both take them from here; set_cost() replaces them for both)
+        self.goal, self.q, self.r = goal4, q4, vec(r, dc, 0.0, "r")
+        for a in (self.goal, self.q, self.r):
+            a.flags.writeable = False
+
+    def set_cost(self, goal=None, q=None, r=None) -> None:
+        """Replace cost parameters (same shapes as the constructor's; None keeps one) for the callables and the device alike."""
+        ds, dc = self.dim_state_model, self.dim_control
+        for name, v, n in (("goal", goal, ds), ("q", q, ds), ("r", r, dc)):
+            if v is None:
+                continue
+            a = _f32(v).reshape(-1)
+            if a.shape != (n,) or not np.all(np.isfinite(a)):
+                raise ValueError(f"{name} must hold {n} finite values")
+            full = np.zeros(len(getattr(self, name)), np.float32)
+            full[:n] = a
+            full.flags.writeable = False
+            setattr(self, name, full)
+        self._torch = {}
+
+    # ------------------------------------------------------------------ weights
+    def _set(self, weights, biases) -> None:
+        Ws, bs = [_f32(w) for w in weights], [_f32(b).reshape(-1) for b in biases]
+        if len(Ws) != len(bs) or len(Ws) not in (2, 3):
+            raise ValueError("an MLP with one or two hidden layers: 2 or 3 weight matrices and as many biases "
+                             f"(got {len(Ws)} and {len(bs)})")
+        if any(w.ndim != 2 for w in Ws) or any(w.shape[0] != b.shape[0] for w, b in zip(Ws, bs)):
+            raise ValueError("every weight is a matrix [out, in] with a bias [out]")
+        if any(w.shape[1] != p.shape[0] for p, w in zip(Ws[:-1], Ws[1:])):
+            raise ValueError("the layers do not chain: each weight's input width is the previous layer's output width")
+        ds = Ws[-1].shape[0]
+        dc = Ws[0].shape[1] - ds
+        if not 1 <= ds <= DS:
+            raise ValueError(f"the network's output (the state) has {ds} components: 1..{DS} run on the device")
+        if dc not in (1, 2):
+            raise ValueError(f"control width {dc} (input width {Ws[0].shape[1]} - state {ds}): 1 or 2 run on the device")
+        if any(w.shape[0] > HIDDEN for w in Ws[:-1]):
+            raise ValueError(f"hidden layers of at most {HIDDEN} units run on the device")
+        if not all(np.all(np.isfinite(a)) for a in Ws + bs):
+            raise ValueError("weights and biases must be finite")
+        if getattr(self, "dim_control", dc) != dc or getattr(self, "dim_state_model", ds) != ds or \
+                getattr(self, "hidden_layers", len(Ws) - 1) != len(Ws) - 1:
+            raise ValueError("update_weights keeps the model's state width, control width and number of layers")
+        self.dim_state_model, self.dim_control, self.hidden_layers = ds, dc, len(Ws) - 1
+        IN = DS + dc
+        # the padded layers of the table: W1[32][IN], b1[32], W2[32][32], b2[32], W3[4][32], b3[4]
+        W1 = np.zeros((HIDDEN, IN), np.float32)
+        W1[:Ws[0].shape[0], :ds] = Ws[0][:, :ds]
+        W1[:Ws[0].shape[0], DS:] = Ws[0][:, ds:]
+        b1 = np.zeros(HIDDEN, np.float32)
+        b1[:bs[0].shape[0]] = bs[0]
+        W2, b2 = np.zeros((HIDDEN, HIDDEN), np.float32), np.zeros(HIDDEN, np.float32)
+        if len(Ws) == 3:
+            W2[:Ws[1].shape[0], :Ws[1].shape[1]] = Ws[1]
+            b2[:bs[1].shape[0]] = bs[1]
+        W3, b3 = np.zeros((DS, HIDDEN), np.float32), np.zeros(DS, np.float32)
+        W3[:ds, :Ws[-1].shape[1]] = Ws[-1]
+        b3[:ds] = bs[-1]
+        self.layers = (W1, b1, W2, b2, W3, b3)
+        self.table = np.concatenate([a.reshape(-1) for a in self.layers]).astype(np.float32)
+        self._torch = {}  # device -> the layers the callables evaluate, as tensors
+
+    def update_weights(self, weights: Sequence, biases: Sequence) -> None:
+        """New weights of the same shapes (a model learned online); the solver uploads them before its next solve."""
+        self._set(weights, biases)
+        self.version += 1
+
+    @classmethod
+    def from_module(cls, module: torch.nn.Module, **kw) -> "MLPModel":
+        """nn.Sequential(Linear, act, [Linear, act,] Linear) with act = nn.ReLU or nn.Tanh (one kind)."""
+        mods = list(module.children()) if not isinstance(module, torch.nn.Linear) else [module]
+        lin = [m for m in mods if isinstance(m, torch.nn.Linear)]
+        acts = [m for m in mods if not isinstance(m, torch.nn.Linear)]
+        kinds = {torch.nn.ReLU: "relu", torch.nn.Tanh: "tanh"}
+        shape_ok = (len(mods) == 2 * len(lin) - 1 and all(isinstance(m, torch.nn.Linear) for m in mods[0::2])
+                    and all(type(m) in kinds for m in acts))
+        if not shape_ok or len(lin) not in (2, 3) or len({type(m) for m in acts}) != 1 or any(m.bias is None for m in lin):
+            raise ValueError("from_module takes nn.Sequential(Linear, act, [Linear, act,] Linear) with biases and "
+                             "act = nn.ReLU or nn.Tanh throughout")
+        return cls([m.weight for m in lin], [m.bias for m in lin], activation=kinds[type(acts[0])], **kw)
+
+    # ------------------------------------------------------------------ what the solver asks for
+    @property
+    def model_name(self) -> str:
+        return "mlp41" if self.dim_control == 1 else "mlp42"
+
+    def native_inputs(self) -> dict:
+        return {"params": [float(v) for v in np.concatenate([self.goal, self.q, self.r])],
+                "mlp": {"table": self.table, "hidden_layers": self.hidden_layers, "activation": self.activation,
+                        "residual": self.residual, "version": self.version}}
+
+    # ------------------------------------------------------------------ the callables
+    def _on(self, ref: torch.Tensor):
+        key = (ref.device, ref.dtype)
+        got = self._torch.get(key)
+        if got is None:
+            got = tuple(torch.tensor(np.array(a)).to(ref.device, ref.dtype) for a in self.layers + (self.goal, self.q, self.r))
+            self._torch[key] = got
+        return got
+
+    def _act(self, z: torch.Tensor) -> torch.Tensor:
+        return torch.tanh(z) if self.activation == "tanh" else torch.clamp_min(z, 0.0)
+
+    @native_model(lambda owner: owner.model_name, "dynamics")
+    def dynamics(self, state: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
+        W1, b1, W2, b2, W3, b3 = self._on(state)[:6]
+        x = torch.cat((state, action), dim=1)
+        z = b1.expand(x.shape[0], HIDDEN)
+        for i in range(x.shape[1]):
+            z = z + W1[:, i] * x[:, i:i + 1]
+        h = self._act(z)
+        if self.hidden_layers == 2:
+            z = b2.expand(x.shape[0], HIDDEN)
+            for i in range(HIDDEN):
+                z = z + W2[:, i] * h[:, i:i + 1]
+            h = self._act(z)
+        o = b3.expand(x.shape[0], DS)
+        for j in range(HIDDEN):
+            o = o + W3[:, j] * h[:, j:j + 1]
+        return state + o if self.residual else o
+
+    @native_model(lambda owner: owner.model_name, "cost", _provider)
+    def cost(self, state: torch.Tensor, action: torch.Tensor, info=None) -> torch.Tensor:
+        goal, q, r = self._on(state)[6:]
+        c = torch.zeros(state.shape[0], device=state.device, dtype=state.dtype)
+        for m in range(DS):
+            d = state[:, m] - goal[m]
+            c = c + q[m] * (d * d)
+        for k in range(self.dim_control):
+            c = c + r[k] * (action[:, k] * action[:, k])
+        return c
+
+    def __deepcopy__(self, memo):
+        new = object.__new__(type(self))
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = {} if k == "_torch" else (tuple(a.copy() for a in v) if k == "layers" else
+                                                        v.copy() if isinstance(v, np.ndarray) else v)
+        for a in (new.goal, new.q, new.r):
+            a.flags.writeable = False
+        return new

@@ -302,6 +302,10 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             if twin is not None:
                 self._recognized = (dynamics, cost_func)  # (kept for inspection; the fused model runs instead)
                 dyn, cst = resolve(twin[0]), resolve(twin[1])
+        if dyn and cst and getattr(dyn[0], "per_owner", False) and dyn[1] is not cst[1]:
+            # a model whose dynamics are its owner's DATA (envs.MLPModel: the weights): the device would take table and
+            # parameters from the cost callable's owner only — two different owners are two different models
+            dyn = cst = None
         if (dyn and cst and dyn[0].model == cst[0].model and dyn[0].role == "dynamics"
                 and cst[0].role == "cost"):
             self._model = dyn[0].model  # fused on the device
@@ -570,6 +574,14 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                 arr = (C.c_float * len(p))(*p)
                 self._h.call("mppi_set_model_params", arr, len(p))
                 self._params_set = p
+        mlp = spec.get("mlp")
+        if mlp is not None:  # learned dynamics: the weight table travels again whenever its owner bumped the version
+            key = (id(self._cost_owner), mlp["version"])
+            if getattr(self._h, "mlp_key", None) != key:  # (kept on the handle: a new handle starts without a table)
+                tab = np.ascontiguousarray(mlp["table"], dtype=np.float32)
+                self._h.call("mppi_set_mlp", tab.ctypes.data_as(C.c_void_p), int(tab.size), int(mlp["hidden_layers"]),
+                             _capi.MLP_ACTIVATIONS[mlp["activation"]], int(bool(mlp["residual"])), self._stream())
+                self._h.mlp_key = key
         for slot, grid in enumerate(spec.get("maps", ())):
             key = (id(grid.cells), grid.version)
             if self._uploaded.get(slot) != key:

@@ -8,7 +8,9 @@ call site `MPPI(..., dynamics=env.dynamics, cost_func=ctrl.cost_function)` stays
     __mppi_native__ = NativeTag(model, role, provider)
 
 where `provider(owner)` returns the model's current inputs as plain host data:
-    {"params": [floats], "maps": [GridSpec, ...], "ref_path": ndarray[rows,4] | None}
+    {"params": [floats], "maps": [GridSpec, ...], "ref_path": ndarray[rows,4] | None,
+     "mlp": {"table": float32[n], "hidden_layers": 1 | 2, "activation": "relu" | "tanh", "residual": bool, "version": int}}
+("mlp": the learned-dynamics models only; the table is uploaded again when `version` changes.)
 `owner` is the bound method's `__self__` (None for plain functions).  The solver calls the provider
 of the cost callable before every solve (the racing reference window changes every tick,
 example/racing.py:73-81) and re-uploads only what changed.
@@ -23,9 +25,11 @@ import numpy as np
 
 @dataclass(frozen=True)
 class NativeTag:
-    model: str                    # "pendulum" | "cartpole" | "mountaincar" | "nav2d" | "racing"
+    model: object                 # a key of _capi.MODEL_IDS ("pendulum", "racing", ...), or model(owner) -> such a key
+                                  # (resolve() calls it: envs/mlp_model.py picks "mlp41" / "mlp42" by its control width)
     role: str                     # "dynamics" | "cost"
     provider: Optional[Callable]  # provider(owner) -> dict
+    per_owner: bool = False       # the model name came from the owner (below): dynamics and cost must share ONE owner
 
 
 @dataclass
@@ -57,4 +61,7 @@ def resolve(fn):
         tag = getattr(fn.__func__, "__mppi_native__", None)
     if not isinstance(tag, NativeTag):
         return None
-    return tag, getattr(fn, "__self__", None)
+    owner = getattr(fn, "__self__", None)
+    if callable(tag.model):
+        tag = NativeTag(tag.model(owner), tag.role, tag.provider, True)
+    return tag, owner
