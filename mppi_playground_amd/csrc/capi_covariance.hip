@@ -69,7 +69,7 @@ int mppi_update_covariance(mppi_handle_t h, float lambda, void* stream) {
     const int blocks = h->reduce.last_reduce_blocks;  // the reduction's own split of the tiles
     const dim3 grid((unsigned)blocks, (unsigned)h->reduce.nchunks);
     hipLaunchKernelGGL(weighted_variance_kernel, grid, dim3(BLOCK), 0, s, h->core.noise, h->core.mean, h->core.costs,
-                       h->core.min_key + h->seq.min_slot, h->reduce.summary, h->wide ? (const float*)h->core.coltab : (const float*)nullptr,
+                       h->min_key.cur(), h->reduce.summary, h->wide ? (const float*)h->core.coltab : (const float*)nullptr,
                        h->cov.part, h->cov.live, h->d, lambda, lam_dev);
     hipLaunchKernelGGL(sigma_update_kernel, dim3(1), dim3(SU_BLOCK), 0, s, h->cov.part, h->cov.live, blocks, h->reduce.colsp,
                        h->d.row, h->dc, h->reduce.summary, h->cov.lim, h->cov.rate, h->cov.floor, sigma_table(h));

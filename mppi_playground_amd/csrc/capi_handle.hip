@@ -152,7 +152,7 @@ int mppi_create(const MppiConfig* cfg, mppi_handle_t* out) {
     auto& c = h->core;
     HIP_TRY(h, c.noise.alloc_set((size_t)d.tiles * d.R * 64, 0));
     HIP_TRY(h, c.costs.alloc((size_t)d.N));
-    HIP_TRY(h, c.min_key.alloc_set(2, 0xFF));
+    HIP_TRY(h, h->min_key.slots.alloc_set(2, 0xFF));
     const size_t x0_floats = (size_t)std::max(md.ds, MPPI_MAX_DIM_STATE);
     HIP_TRY(h, c.x0.alloc_set(x0_floats, 0));
     c.x0_cur = c.x0;
@@ -261,7 +261,7 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
     auto &dc = dst->core, &sc = src->core;
     if (sc.tiles_valid) CLONE(core.noise);
     CLONE(core.costs);
-    CLONE(core.min_key);
+    CLONE(min_key.slots);
     if (int rc = clone_buf(dst, dc.x0.p, sc.x0_cur, (size_t)src->ds)) return rc;  // (a borrowed state becomes an owned copy)
     dc.x0_cur = dc.x0;
     CLONE(core.x0_used);
@@ -288,7 +288,7 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
     CLONE(search.lambda_dev);
     if (src->fused.grid0 && !dst->fused.grid0) HIP_TRY(dst, dst->fused.grid0.alloc(STATS_L));
     CLONE(fused.grid0);
-    dst->seq.min_slot = src->seq.min_slot; dc.gen = sc.gen; dc.tiles_valid = sc.tiles_valid; dc.injected = sc.injected;
+    dst->min_key.idx = src->min_key.idx; dc.gen = sc.gen; dc.tiles_valid = sc.tiles_valid; dc.injected = sc.injected;
     dst->opt = src->opt;
     auto &ds = dst->search, &ss = src->search;
     ds.auto_rule = ss.auto_rule; ds.auto_param = ss.auto_param; ds.auto_lo = ss.auto_lo; ds.auto_hi = ss.auto_hi;

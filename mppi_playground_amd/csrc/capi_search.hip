@@ -68,7 +68,7 @@ __global__ __launch_bounds__(BRENT_THREADS) void lbps_brent_kernel(const float* 
                                                                    double delta, double lam_min, double lam_max, BrentCtx bx,
                                                                    float* __restrict__ lambda_out,
                                                                    double* __restrict__ lambda_host /*[3]: next, used, probes*/) {
-    extern __shared__ float s_cost[];  // [per_thread][blockDim.x] when staged
+    extern __shared__ float s_cost[];  // BrentStageLds: [per_thread][blockDim.x] when staged
     __shared__ BrentLds L;
     const int tid = threadIdx.x;
     const bool staged = per_thread <= BRENT_STAGE_MAX;
@@ -220,7 +220,7 @@ extern "C" {
 int mppi_softmax_stats(mppi_handle_t h, float lambda, double* out5_host, void* stream) {
     if (!h || !out5_host || !(lambda > 0.0f)) return fail(h, MPPI_E_INVALID, "bad softmax_stats arguments");
     hipStream_t s = (hipStream_t)stream;
-    const unsigned* mk = h->core.min_key + h->seq.min_slot;
+    const unsigned* mk = h->min_key.cur();
     const int blocks = stats_blocks(h, BLOCK);
     hipLaunchKernelGGL(stats_partial_kernel, dim3(blocks), dim3(BLOCK), 0, s, h->core.costs, h->d.N, mk, lambda,
                        (const float*)nullptr, h->search.stats_part);
@@ -242,7 +242,7 @@ int mppi_softmax_stats_multi(mppi_handle_t h, const float* lambdas_host, int cou
     }
     hipStream_t s = (hipStream_t)stream;
     if (int rc = upload_small(h, h->search.lams_dev, lam, STATS_L, s)) return rc;
-    const unsigned* mk = h->core.min_key + h->seq.min_slot;
+    const unsigned* mk = h->min_key.cur();
     const int blocks = stats_blocks(h);
     hipLaunchKernelGGL(stats_multi_kernel, dim3(blocks), dim3(STATS_THREADS), 0, s, h->core.costs, h->d.N, mk,
                        (const float*)h->search.lams_dev, h->search.stats_part, (float*)nullptr);
@@ -262,7 +262,7 @@ int mppi_essps_lambda_device(mppi_handle_t h, double target_ess, double lam_min,
     if (int rc = check_essps(h, h != nullptr, target_ess, lam_min, lam_max)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = essps_prepare(h, lam_min, lam_max)) return rc;
-    const unsigned* mk = h->core.min_key + h->seq.min_slot;
+    const unsigned* mk = h->min_key.cur();
     const int blocks = stats_blocks(h);
     double* host_lam = &h->search.mirror.dev->lam_next;
     float* lams0 = h->search.lams_dev + STATS_L;
@@ -321,7 +321,7 @@ int mppi_lbps_lambda_device(mppi_handle_t h, double delta, double lam_min, doubl
     }
     // the caller's-grid slot may have been overwritten by mppi_softmax_stats_multi: refresh it
     if (int rc = upload_small(h, lams0, lamf, STATS_L, s)) return rc;
-    const unsigned* mk = h->core.min_key + h->seq.min_slot;
+    const unsigned* mk = h->min_key.cur();
     const int blocks = stats_blocks(h);
     for (int r = 0; r < LBPS_ROUNDS; ++r) {
         hipLaunchKernelGGL(stats_multi_kernel, dim3(blocks), dim3(STATS_THREADS), 0, s, h->core.costs, h->d.N, mk,
@@ -379,7 +379,7 @@ int mppi_lbps_brent_device(mppi_handle_t h, double delta, double lam_min, double
     const int threads = BLOCK * ((nvb + BRENT_LANES - 1) / BRENT_LANES);
     if (grid > h->cu_count) return fail(h, MPPI_E_STATE, "lbps_brent: more blocks than CUs (they must be resident at once)");
     int per_thread = (int)std::min<int64_t>(per_thread64, BRENT_STAGE_MAX + 1);  // (beyond the staging limit only the flag matters)
-    size_t shmem = per_thread <= BRENT_STAGE_MAX ? sizeof(float) * (size_t)per_thread * threads : 0;
+    size_t shmem = per_thread <= BRENT_STAGE_MAX ? sizeof(float) * BrentStageLds::floats(per_thread, threads) : 0;
     if (shmem + sizeof(BrentLds) + 256 > (size_t)h->lds_max) { per_thread = BRENT_STAGE_MAX + 1; shmem = 0; }
     if (shmem > 48 * 1024) {
         static size_t granted = 0;  // (per process: the attribute belongs to the kernel, not to a handle)
@@ -398,7 +398,7 @@ int mppi_lbps_brent_device(mppi_handle_t h, double delta, double lam_min, double
     // (test hook: with the last block missing, its lane's sums never arrive — what a block that is not resident looks like to
     // the others: every poll runs into the budget, the flag is raised and the temperature is NaN)
     hipLaunchKernelGGL(lbps_brent_kernel, dim3(grid - (h->search.brent_drop_block && grid > 1 ? 1 : 0)), dim3(threads), shmem, s, (const float*)h->core.costs, h->d.N,
-                       (const unsigned*)(h->core.min_key + h->seq.min_slot), nvb, per_thread, delta, lam_min, lam_max, bx, h->search.lambda_dev,
+                       h->min_key.cur(), nvb, per_thread, delta, lam_min, lam_max, bx, h->search.lambda_dev,
                        &h->search.mirror.dev->lam_next);
     HIP_TRY(h, hipGetLastError());
     h->search.lambda_dev_valid = true;
@@ -448,7 +448,7 @@ int mppi_mpo_reset(mppi_handle_t h, double lambda0, double epsilon, double lr) {
 int mppi_mpo_step_device(mppi_handle_t h, void* stream) {
     if (!h) return MPPI_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    const unsigned* mk = h->core.min_key + h->seq.min_slot;
+    const unsigned* mk = h->min_key.cur();
     const int blocks = stats_blocks(h, BLOCK);
     hipLaunchKernelGGL(stats_partial_kernel, dim3(blocks), dim3(BLOCK), 0, s, h->core.costs, h->d.N, mk, 1.0f,
                        (const float*)h->search.mpo_temp_dev, h->search.stats_part);

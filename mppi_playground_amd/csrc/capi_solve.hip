@@ -76,19 +76,14 @@ __global__ __launch_bounds__(SUM_BLOCK) void summarize_kernel(const float* __res
 // beyond it the multi-block summarize_kernel is cheaper than one block walking the rows.
 static constexpr int FOLD_IN_FINALIZE_MAX_ROWS = 64;
 
-// dynamic LDS of finalize_kernel: [row] action, [W][4 + row] summaries, the Savitzky-Golay staging and — when the
-// kernel folds the partial rows itself — [64][row + 3] group sums (see finalize_kernel)
-static size_t finalize_lds_floats(mppi_handle_t h, int world, int sg_window, bool fold) {
-    return (size_t)h->d.row + (size_t)world * (h->d.row + MPPI_SUMMARY_HEAD) +
-           (sg_window ? (size_t)(2 * h->d.T - 1 + 2 * (sg_window / 2)) * h->dc : 0) +
-           (fold ? (size_t)(SUM_BLOCK / SUM_COLS) * (h->d.row + 3) : 0);
-}
-
 // Short rows fold inside finalize_kernel (sparse softmax: no summarize launch); rows whose group sums do not fit the
 // 64 KiB of LDS always take summarize_kernel.  A static property of the handle: the choice never depends on timing.
 static bool fold_fits(mppi_handle_t h) {
-    return finalize_lds_floats(h, 1, 255 /* widest filter */, true) * sizeof(float) <= 64 * 1024;
+    return FinalizeLds::floats(h->d.T, h->d.row, h->dc, 1, 255 /* widest filter */, true) * sizeof(float) <= 64 * 1024;
 }
+
+// grid of the layout conversions (inject_kernel, export_kernel): one block per tile and CONV_COLS columns of the row
+static dim3 conv_grid(mppi_handle_t h) { return dim3((unsigned)h->d.tiles, (unsigned)((h->d.row + CONV_COLS - 1) / CONV_COLS)); }
 
 // (`tm`: the stage the launch belongs to, or an untimed one)
 static int materialize_tiles(mppi_handle_t h, StageTimer& tm) {
@@ -149,7 +144,7 @@ int flush_state_seq(mppi_handle_t h, hipStream_t s) {
     if (!h->lazy.pending_out) return MPPI_OK;
     float* out = h->lazy.pending_out;
     if (int rc = order_behind_pending(h, s)) return rc;
-    const size_t sh1 = sizeof(float) * ((size_t)h->d.row + MPPI_MAX_DIM_STATE);
+    const size_t sh1 = sizeof(float) * StateSeqLds::floats(h->d.row);
     StageTimer tm(h, 4, s);
 #define CALL_STATE_SEQ(MODEL, FASTV)                                                                  \
     tm.launch(state_seq_kernel<MODEL, FASTV>, dim3(1), dim3(WAVE), sh1, (const float*)h->lazy.b1, h->d.row, h->d.T, out, h->model.ctx)
@@ -207,11 +202,11 @@ static int solve_fused(mppi_handle_t h, float lambda, float* action_out, float* 
         h->fused.grid0_lo = h->search.auto_lo; h->fused.grid0_hi = h->search.auto_hi;
     }
     if (!dev && !(lambda > 0.0f)) return fail(h, MPPI_E_INVALID, "lambda must be > 0");
-    h->seq.min_slot ^= 1;
+    const auto mk = h->min_key.begin_rollout();
     next_tag(h->seq.fused);
     FusedArgs A{};
     A.mean = h->core.mean; A.x0 = h->core.x0_cur; A.costs = h->core.costs;
-    A.min_key = h->core.min_key + h->seq.min_slot; A.next_min_key = h->core.min_key + (h->seq.min_slot ^ 1);
+    A.min_key = mk.accumulate; A.next_min_key = mk.reset_next;
     A.mean_used = h->core.mean_used; A.x0_used = h->core.x0_used;
     A.rule = rule; A.rule_param = h->search.auto_param; A.lam_min = h->search.auto_lo; A.lam_max = h->search.auto_hi;
     A.lambda_arg = dev ? -1.0f : lambda;
@@ -236,8 +231,7 @@ static int solve_fused(mppi_handle_t h, float lambda, float* action_out, float* 
     h->fused.last_blocks = (int)grid; h->fused.last_spb = A.spb;  // (mppi_fused_geometry; cleared by mppi_solve if the launch is declined)
 #define CALL_FUSED(MODEL, FASTV)                                                                      \
     do {                                                                                              \
-        const size_t shmem = sizeof(float) * ((size_t)8 * h->d.R + (size_t)h->d.T * ModelT<MODEL, FASTV>::KROW + 2 * (size_t)h->d.row + \
-                                              MPPI_SUMMARY_HEAD + (sg.window ? (size_t)(2 * h->d.T - 1 + 2 * (sg.window / 2)) * h->dc : 0)); \
+        const size_t shmem = sizeof(float) * FusedLds::floats(h->d.R, h->d.T, h->d.row, h->dc, ModelT<MODEL, FASTV>::KROW, sg.window); \
         /* the blocks synchronise through cells in HBM: every one of them must be resident at once.  Checked against the   \
            kernel's own occupancy (cached per (math level, LDS size)); what OTHER work holds of the GPU at run time is what  \
            the polls' time-out is for */                                                                                   \
@@ -254,7 +248,7 @@ static int solve_fused(mppi_handle_t h, float lambda, float* action_out, float* 
     MPPI_DISPATCH(h, CALL_FUSED);
 #undef CALL_FUSED
     if (*declined) {  // (undo the bookkeeping of a solve that did not start: the multi-kernel path takes it from here)
-        h->seq.min_slot ^= 1;
+        h->min_key.cancel_rollout();
         --h->seq.fused;
         return MPPI_OK;
     }
@@ -277,7 +271,8 @@ int mppi_sample(mppi_handle_t h, uint32_t solve_idx, void* stream) {
     h->core.gen.solve_idx = solve_idx;
     h->core.injected = false;
     h->core.tiles_valid = false;
-    if (h->opt.noise_regen && !h->wide && !tiles_only(h)) return MPPI_OK;  // consumers regenerate eps(seed, solve, i, t, k) in registers
+    // (`injected` was cleared two lines up, so this is the handle's standing answer)
+    if (regen_noise(h)) return MPPI_OK;  // consumers regenerate eps(seed, solve, i, t, k) in registers
     StageTimer tm(h, 0, s);
     return materialize_tiles(h, tm);
 }
@@ -285,8 +280,7 @@ int mppi_sample(mppi_handle_t h, uint32_t solve_idx, void* stream) {
 int mppi_inject_noise(mppi_handle_t h, const float* eps_dev, void* stream) {
     if (!h || !eps_dev) return fail(h, MPPI_E_INVALID, "null");
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)h->d.tiles, (unsigned)((h->d.row + CONV_COLS - 1) / CONV_COLS));
-    hipLaunchKernelGGL(inject_kernel, grid, dim3(BLOCK), 0, s, eps_dev, h->core.noise, h->d);
+    hipLaunchKernelGGL(inject_kernel, conv_grid(h), dim3(BLOCK), 0, s, eps_dev, h->core.noise, h->d);
     HIP_TRY(h, hipGetLastError());
     h->core.injected = true;
     h->core.tiles_valid = true;
@@ -297,8 +291,7 @@ int mppi_export_noise(mppi_handle_t h, float* eps_out, float* act_out, void* str
     if (!h) return MPPI_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = need_tiles(h, s)) return rc;
-    const dim3 grid((unsigned)h->d.tiles, (unsigned)((h->d.row + CONV_COLS - 1) / CONV_COLS));
-    hipLaunchKernelGGL(export_kernel, grid, dim3(BLOCK), 0, s, h->core.noise, h->core.mean, eps_out, act_out, h->d,
+    hipLaunchKernelGGL(export_kernel, conv_grid(h), dim3(BLOCK), 0, s, h->core.noise, h->core.mean, eps_out, act_out, h->d,
                        h->wide ? h->core.coltab : (const float*)nullptr);
     HIP_TRY(h, hipGetLastError());
     return MPPI_OK;
@@ -313,22 +306,19 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
         if (int rc = flush_state_seq(h, s)) return rc;
         if (!h->core.noise_std) HIP_TRY(h, h->core.noise_std.alloc((size_t)h->d.N * h->d.row));
         if (int rc = need_tiles(h, s)) return rc;
-        const dim3 cgrid((unsigned)h->d.tiles, (unsigned)((h->d.row + CONV_COLS - 1) / CONV_COLS));
-        hipLaunchKernelGGL(export_kernel, cgrid, dim3(BLOCK), 0, s, h->core.noise, h->core.mean, h->core.noise_std, (float*)nullptr, h->d,
+        hipLaunchKernelGGL(export_kernel, conv_grid(h), dim3(BLOCK), 0, s, h->core.noise, h->core.mean, h->core.noise_std, (float*)nullptr, h->d,
                            (const float*)nullptr);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipMemcpyAsync(h->core.mean_used, h->core.mean, sizeof(float) * (size_t)h->d.row, hipMemcpyDeviceToDevice, s));
         HIP_TRY(h, hipMemcpyAsync(h->core.x0_used, h->core.x0_cur, sizeof(float) * (size_t)h->ds, hipMemcpyDeviceToDevice, s));
         StageTimer tmw(h, 1, s);
-        h->seq.min_slot ^= 1;
-        unsigned* mkw = h->core.min_key + h->seq.min_slot;
-        unsigned* mkw_next = h->core.min_key + (h->seq.min_slot ^ 1);
+        const auto mkw = h->min_key.begin_rollout();
         const unsigned wgrid = (unsigned)std::min<int64_t>((h->d.N + 3) / 4, 256 * 8 * 4);
 #define CALL_WAVE(MODEL, FASTV)                                                                       \
         do {                                                                                          \
-            const size_t shw = sizeof(float) * 4 * ((size_t)4 * h->d.R + (size_t)(h->d.T + 1) * ModelT<MODEL, FASTV>::DS); \
+            const size_t shw = sizeof(float) * WaveRolloutLds::floats(h->d.R, h->d.T, ModelT<MODEL, FASTV>::DS);          \
             tmw.launch(rollout_cost_wave_kernel<MODEL, FASTV>, dim3(wgrid), dim3(BLOCK), shw, h->core.noise_std,      \
-                       h->core.mean, h->core.x0_cur, h->core.costs, mkw, mkw_next, h->d, h->model.ctx);                 \
+                       h->core.mean, h->core.x0_cur, h->core.costs, mkw.accumulate, mkw.reset_next, h->d, h->model.ctx); \
         } while (0)
         MPPI_DISPATCH(h, CALL_WAVE);
 #undef CALL_WAVE
@@ -336,11 +326,9 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
         return MPPI_OK;
     }
     StageTimer tm(h, 1, s, true);  // (this stage's one kernel stamps its own time)
-    const bool gen = h->opt.noise_regen && !h->core.injected && !tiles_only(h);
+    const bool gen = regen_noise(h);  // (check_ready has refused generic handles, the only wide ones)
     if (!gen && !h->core.tiles_valid) return fail(h, MPPI_E_STATE, "no noise: call mppi_sample or mppi_inject_noise first");
-    h->seq.min_slot ^= 1;
-    unsigned* mk = h->core.min_key + h->seq.min_slot;
-    unsigned* mk_next = h->core.min_key + (h->seq.min_slot ^ 1);
+    const auto mk = h->min_key.begin_rollout();
     // a state sequence still pending from the previous solve (option "lazy_state_seq") rides in one extra block of this
     // launch: its T dependent steps hide behind the N-sample rollout instead of extending the previous solve's tail
     float* ride = h->lazy.pending_out;
@@ -349,30 +337,23 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
     unsigned long long* stamps = tm.take_stamps();
     const bool term = h->ac.on;  // the control-cost term: its own instantiations, 4R more floats of LDS for g
     const ActionCostArgs aca = action_cost_args(h, h->ac.lambda);
+#define ROLLOUT_ARGS                                                                                  \
+    h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk.accumulate, mk.reset_next, h->core.mean_used, h->core.x0_used, \
+    h->d, h->core.gen, h->model.ctx, (const float*)h->lazy.b1, ride, stamps
 #define CALL_ROLLOUT(MODEL, FASTV)                                                                    \
     do {                                                                                              \
-        const size_t shmem = sizeof(float) * std::max((size_t)(term ? 12 : 8) * h->d.R + (size_t)h->d.T * ModelT<MODEL, FASTV>::KROW, \
-                                                      (size_t)h->d.row + MPPI_MAX_DIM_STATE);         \
+        const size_t shmem = sizeof(float) * RolloutLds::floats(h->d.R, h->d.T, h->d.row, ModelT<MODEL, FASTV>::KROW, term); \
         constexpr bool UCV = FASTV != 0;  /* the FAST kernels exist in the u_in_bounds form only (see use_fast) */ \
-        if (term && gen)                                                                              \
-            tm.launch(rollout_action_cost_kernel<MODEL, FASTV, true, UCV>, dim3(grid), dim3(BLOCK), shmem,     \
-                      h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
-                      (const float*)h->lazy.b1, ride, stamps, aca);                                              \
-        else if (term)                                                                                \
-            tm.launch(rollout_action_cost_kernel<MODEL, FASTV, false, UCV>, dim3(grid), dim3(BLOCK), shmem,    \
-                      h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
-                      (const float*)h->lazy.b1, ride, stamps, aca);                                              \
-        else if (gen)                                                                                 \
-            tm.launch(rollout_cost_kernel<MODEL, FASTV, true, UCV>, dim3(grid), dim3(BLOCK), shmem,     \
-                      h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
-                      (const float*)h->lazy.b1, ride, stamps);                                                   \
+        if (term)                                                                                     \
+            tm.launch(gen ? rollout_action_cost_kernel<MODEL, FASTV, true, UCV> : rollout_action_cost_kernel<MODEL, FASTV, false, UCV>, \
+                      dim3(grid), dim3(BLOCK), shmem, ROLLOUT_ARGS, aca);                             \
         else                                                                                          \
-            tm.launch(rollout_cost_kernel<MODEL, FASTV, false, UCV>, dim3(grid), dim3(BLOCK), shmem,    \
-                      h->core.noise, h->core.mean, h->core.x0_cur, h->core.costs, mk, mk_next, h->core.mean_used, h->core.x0_used, h->d, h->core.gen, h->model.ctx, \
-                      (const float*)h->lazy.b1, ride, stamps);                                                   \
+            tm.launch(gen ? rollout_cost_kernel<MODEL, FASTV, true, UCV> : rollout_cost_kernel<MODEL, FASTV, false, UCV>, \
+                      dim3(grid), dim3(BLOCK), shmem, ROLLOUT_ARGS);                                  \
     } while (0)
     MPPI_DISPATCH(h, CALL_ROLLOUT);
 #undef CALL_ROLLOUT
+#undef ROLLOUT_ARGS
     HIP_TRY(h, hipGetLastError());
     if (ride) h->lazy.pending_out = nullptr;  // (cleared only once the launch that carries it went through)
     return MPPI_OK;
@@ -399,15 +380,20 @@ __global__ void min_cost_kernel(const float* __restrict__ costs, int64_t N, unsi
     if ((threadIdx.x & 63) == 0 && m < INFINITY) atomicMin(min_key, float_to_key(m));
 }
 
+// The costs were replaced by something other than a rollout: the current minimum key is computed from them again.
+static int refresh_min_key(mppi_handle_t h, hipStream_t s) {
+    HIP_TRY(h, hipMemsetAsync(h->min_key.cur_rw(), 0xFF, sizeof(unsigned), s));
+    const unsigned grid = (unsigned)std::min<int64_t>((h->d.N + BLOCK - 1) / BLOCK, 1024);
+    hipLaunchKernelGGL(min_cost_kernel, dim3(grid), dim3(BLOCK), 0, s, h->core.costs, h->d.N, h->min_key.cur_rw());
+    HIP_TRY(h, hipGetLastError());
+    return MPPI_OK;
+}
+
 int mppi_set_costs(mppi_handle_t h, const float* src, int on_device, void* stream) {
     if (!h || !src) return fail(h, MPPI_E_INVALID, "null");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = copy_small(h, h->core.costs, src, sizeof(float) * (size_t)h->d.N, true, on_device != 0, s)) return rc;
-    HIP_TRY(h, hipMemsetAsync(h->core.min_key + h->seq.min_slot, 0xFF, sizeof(unsigned), s));
-    const unsigned grid = (unsigned)std::min<int64_t>((h->d.N + BLOCK - 1) / BLOCK, 1024);
-    hipLaunchKernelGGL(min_cost_kernel, dim3(grid), dim3(BLOCK), 0, s, h->core.costs, h->d.N, h->core.min_key + h->seq.min_slot);
-    HIP_TRY(h, hipGetLastError());
-    return MPPI_OK;
+    return refresh_min_key(h, s);
 }
 
 // costs[i] += kappa * A_i from the noise tiles: the control-cost term as a pass of its own (mppi_add_action_cost).  One
@@ -458,30 +444,30 @@ int mppi_set_action_cost(mppi_handle_t h, int enable, float weight) {
     return MPPI_OK;
 }
 
-int mppi_set_action_cost_lambda(mppi_handle_t h, float lambda) {
-    if (!h) return MPPI_E_INVALID;
+// the temperature argument of the control-cost entry points
+static int check_action_cost_lambda(mppi_handle_t h, float lambda) {
     if (lambda != MPPI_LAMBDA_DEVICE && (!(lambda >= 0.0f) || !std::isfinite(lambda)))
         return fail(h, MPPI_E_INVALID, "control-cost term: lambda must be >= 0 or MPPI_LAMBDA_DEVICE");
+    return MPPI_OK;
+}
+
+int mppi_set_action_cost_lambda(mppi_handle_t h, float lambda) {
+    if (!h) return MPPI_E_INVALID;
+    if (int rc = check_action_cost_lambda(h, lambda)) return rc;
     h->ac.lambda = lambda;
     return MPPI_OK;
 }
 
 int mppi_add_action_cost(mppi_handle_t h, float lambda, void* stream) {
     if (!h) return MPPI_E_INVALID;
-    if (lambda != MPPI_LAMBDA_DEVICE && (!(lambda >= 0.0f) || !std::isfinite(lambda)))
-        return fail(h, MPPI_E_INVALID, "control-cost term: lambda must be >= 0 or MPPI_LAMBDA_DEVICE");
+    if (int rc = check_action_cost_lambda(h, lambda)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = need_tiles(h, s)) return rc;
     const unsigned agrid = (unsigned)((h->d.N + BLOCK - 1) / BLOCK);
     hipLaunchKernelGGL(action_cost_kernel, dim3(agrid), dim3(BLOCK), 0, s, h->core.noise, h->core.mean, h->core.costs, h->d,
                        h->wide ? (const float*)h->core.coltab : (const float*)nullptr, action_cost_args(h, lambda));
     HIP_TRY(h, hipGetLastError());
-    // the minimum key, the way mppi_set_costs refreshes it
-    HIP_TRY(h, hipMemsetAsync(h->core.min_key + h->seq.min_slot, 0xFF, sizeof(unsigned), s));
-    const unsigned grid = (unsigned)std::min<int64_t>((h->d.N + BLOCK - 1) / BLOCK, 1024);
-    hipLaunchKernelGGL(min_cost_kernel, dim3(grid), dim3(BLOCK), 0, s, h->core.costs, h->d.N, h->core.min_key + h->seq.min_slot);
-    HIP_TRY(h, hipGetLastError());
-    return MPPI_OK;
+    return refresh_min_key(h, s);
 }
 
 int mppi_weights_reduce(mppi_handle_t h, float lambda, float* summary_out_dev, void* stream) {
@@ -508,7 +494,7 @@ int mppi_weights_reduce(mppi_handle_t h, float lambda, float* summary_out_dev, v
     const dim3 grid((unsigned)blocks, (unsigned)h->reduce.nchunks);
     const bool gen = regen_noise(h);
     if (!gen && !h->core.tiles_valid) return fail(h, MPPI_E_STATE, "no noise: call mppi_sample or mppi_inject_noise first");
-    const unsigned* mk = h->core.min_key + h->seq.min_slot;
+    const unsigned* mk = h->min_key.cur();
 #define CALL_REDUCE(GPWV, GENV, WIDEV, CHAINSV, REMV)                                                 \
     tm.launch(weights_reduce_kernel<GPWV, GENV, WIDEV, CHAINSV, REMV>, grid, dim3(BLOCK), 0, h->core.noise, h->core.mean, h->core.costs, mk, \
               h->reduce.partials, h->reduce.heads, h->d, h->core.gen, lambda, lam_dev, (const float*)h->core.coltab)
@@ -570,9 +556,9 @@ int mppi_finalize(mppi_handle_t h, const float* summaries_dev, int num_shards, f
     // the filter replaces the stored warm start, so it only runs when this call stores it (mppi.py:441-452)
     const SgFilter sg{h->reduce.sg_coeffs, h->reduce.sg_history, (store_mean && h->reduce.sg_window > 0) ? h->reduce.sg_window : 0};
     const bool fold_here = !summaries_dev && !p2p.seq;  // the kernel folds the partial rows itself
-    const size_t shmem = finalize_lds_floats(h, p2p.seq ? p2p.world : 1, sg.window, fold_here) * sizeof(float);
+    const size_t shmem = FinalizeLds::floats(h->d.T, h->d.row, h->dc, p2p.seq ? p2p.world : 1, sg.window, fold_here) * sizeof(float);
     if (shmem > 64 * 1024) return fail(h, MPPI_E_INVALID, "finalize: horizon too long for the exchange / filter staging");
-    const unsigned* mk = h->core.min_key + h->seq.min_slot;
+    const unsigned* mk = h->min_key.cur();
     // Option "lazy_state_seq": the batch-1 rollout leaves this kernel (and the solve's critical path).  The kernel writes the
     // rollout's inputs to h->lazy.b1; the rollout itself rides in the next mppi_rollout_cost launch on this stream, or is
     // launched by mppi_join_state_seq when somebody reads the state sequence first.

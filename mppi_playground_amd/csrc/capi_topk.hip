@@ -74,7 +74,7 @@ static int check_row_lds(mppi_handle_t h, const void* kernel, size_t dyn, const 
 // h->topk.cand when k > TOPK_MAX (sorted in place).
 static int topk_rollout(mppi_handle_t h, const unsigned long long* cand, int k, float lambda, float* states_out,
                         float* weights_out, bool clean, bool need_local, hipStream_t s, bool direct = false) {
-    const bool gen = h->opt.noise_regen && !h->core.injected && !tiles_only(h);
+    const bool gen = regen_noise(h);  // (every caller has refused generic handles, the only wide ones: check_ready)
     if (!gen && !h->core.tiles_valid) return fail(h, MPPI_E_STATE, "no noise: solve first");
     if (!gen && !need_local)
         return fail(h, MPPI_E_STATE, "candidates of other shards can only be re-rolled from regenerated noise (noise_regen = 1, no injection)");
@@ -82,8 +82,8 @@ static int topk_rollout(mppi_handle_t h, const unsigned long long* cand, int k, 
     unsigned* counters = clean ? h->topk.hist + 3 * TOPK_BINS : nullptr;
     if (k <= TOPK_MAX) {
 #define CALL_TOPK(MODEL, FASTV)                                                                       \
-    if (int rc = check_row_lds(h, (const void*)topk_rollout_kernel<MODEL, FASTV, false>, topk_rollout_lds(h->d.R, false, gen), "get_top_samples")) return rc; \
-    hipLaunchKernelGGL((topk_rollout_kernel<MODEL, FASTV, false>), dim3((unsigned)((k + WAVE - 1) / WAVE)), dim3(TOPK_MAX), topk_rollout_lds(h->d.R, false, gen), s, cand, k, \
+    if (int rc = check_row_lds(h, (const void*)topk_rollout_kernel<MODEL, FASTV, false>, sizeof(float) * TopkLds::floats(h->d.R, false, gen), "get_top_samples")) return rc; \
+    hipLaunchKernelGGL((topk_rollout_kernel<MODEL, FASTV, false>), dim3((unsigned)((k + WAVE - 1) / WAVE)), dim3(TOPK_MAX), sizeof(float) * TopkLds::floats(h->d.R, false, gen), s, cand, k, \
                        direct ? (const float*)h->core.costs : (const float*)nullptr, direct ? (int)h->d.N : 0, h->core.noise, gen,  \
                        h->core.mean_used, h->core.x0_used, h->reduce.solve_stats, lambda, states_out, weights_out, hist, counters,  \
                        h->d, h->core.gen, h->model.ctx)
@@ -93,8 +93,8 @@ static int topk_rollout(mppi_handle_t h, const unsigned long long* cand, int k, 
         if (int rc = topk_sort_large(h, k, s)) return rc;
         const unsigned grid = (unsigned)((k + WAVE - 1) / WAVE);
 #define CALL_TOPK_SORTED(MODEL, FASTV)                                                                \
-    if (int rc = check_row_lds(h, (const void*)topk_rollout_kernel<MODEL, FASTV, true>, topk_rollout_lds(h->d.R, true, gen), "get_top_samples")) return rc; \
-    hipLaunchKernelGGL((topk_rollout_kernel<MODEL, FASTV, true>), dim3(grid), dim3(WAVE), topk_rollout_lds(h->d.R, true, gen), s, (const unsigned long long*)h->topk.cand, \
+    if (int rc = check_row_lds(h, (const void*)topk_rollout_kernel<MODEL, FASTV, true>, sizeof(float) * TopkLds::floats(h->d.R, true, gen), "get_top_samples")) return rc; \
+    hipLaunchKernelGGL((topk_rollout_kernel<MODEL, FASTV, true>), dim3(grid), dim3(WAVE), sizeof(float) * TopkLds::floats(h->d.R, true, gen), s, (const unsigned long long*)h->topk.cand, \
                        k, (const float*)nullptr, 0, h->core.noise, gen, h->core.mean_used, h->core.x0_used, h->reduce.solve_stats, lambda, states_out,  \
                        weights_out, hist, counters, h->d, h->core.gen, h->model.ctx)
         MPPI_DISPATCH(h, CALL_TOPK_SORTED);

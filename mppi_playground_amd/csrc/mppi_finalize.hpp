@@ -2,6 +2,7 @@
 // Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include "mppi_exchange.hpp"
+#include "mppi_lds.hpp"
 #include "mppi_reduce.hpp"
 
 namespace mppi {
@@ -209,10 +210,10 @@ template <int MODEL, int FAST>
 __global__ __launch_bounds__(WAVE) void state_seq_kernel(const float* __restrict__ b1_in, int row, int T,
                                                          float* __restrict__ state_out, ModelCtx ctx) {
     constexpr int DS = ModelT<MODEL, FAST>::DS;
-    extern __shared__ __attribute__((aligned(16))) float s_b1[];  // [row] action, [DS] start state
+    extern __shared__ __attribute__((aligned(16))) float s_b1[];  // StateSeqLds: [row] action, [DS] start state
     for (int i = threadIdx.x; i < row + DS; i += WAVE) s_b1[i] = b1_in[i];
     __syncthreads();
-    batch1_rollout<MODEL, FAST>(ctx, s_b1 + row, s_b1, T, state_out);
+    batch1_rollout<MODEL, FAST>(ctx, s_b1 + StateSeqLds::x0(row), s_b1, T, state_out);
 }
 
 constexpr int FIN_BLOCK = 1024;
@@ -341,12 +342,12 @@ __global__ __launch_bounds__(FIN_BLOCK) void finalize_kernel(const float* __rest
     const unsigned min_key_now = *min_key;
     __shared__ float s_x0[MPPI_MAX_DIM_STATE];
     if (threadIdx.x < ModelT<MODEL, FAST>::DS) s_x0[threadIdx.x] = x0[threadIdx.x];
-    // [row] action, [max(1, W) * (4 + row)] own / collected summaries, then (SG filter) [(2T-1+2*(w/2))*dc]
+    // FinalizeLds: [row] action, [max(1, W) * (4 + row)] own / collected summaries, then (SG filter) [(2T-1+2*(w/2))*dc]
     extern __shared__ __attribute__((aligned(16))) float s_fin[];
     const int stride = MPPI_SUMMARY_HEAD + row;
     float* s_act = s_fin;
-    float* s_sum = s_fin + row;
-    float* s_yp = s_sum + (p2p.seq ? p2p.world : 1) * stride;
+    float* s_sum = s_fin + FinalizeLds::sum(row);
+    float* s_yp = s_sum + (p2p.seq ? p2p.world : 1) * stride;  // (FinalizeLds::yp)
     if (p2p.seq) {  // the shards' summaries arrive through the peer-to-peer exchange buffer
         __shared__ int s_timed_out;
         if (threadIdx.x == 0) s_timed_out = 0;
@@ -366,11 +367,13 @@ __global__ __launch_bounds__(FIN_BLOCK) void finalize_kernel(const float* __rest
         num_shards = p2p.world;
     } else if (summaries == nullptr) {
         constexpr int NG = SUM_BLOCK / SUM_COLS;  // 64 row groups: summarize_kernel's tree
+        static_assert(NG == FinalizeLds::FOLD_GROUPS, "the launch site sizes the group sums for summarize_kernel's tree");
         __shared__ unsigned short s_list[REDUCE_MAX_BLOCKS];
         __shared__ int s_wcnt[REDUCE_MAX_BLOCKS / WAVE];
         const int nlive = compact_live_rows<FIN_BLOCK>(heads, nblocks, s_list, s_wcnt);
         const int ncols = row + 3;  // the last 3 "columns" are the heads
         // [NG][ncols] group sums, behind the filter staging (the host sizes the dynamic LDS for it)
+        // (FinalizeLds::fold, written out: as an argument of sg_staging_floats the division row / T would run without a filter too)
         float* s_fold = s_yp + (sg.window ? (2 * T - 1 + 2 * (sg.window / 2)) * (row / T) : 0);
         // row groups g >= nlive hold no row: their sums are +0 and adding them changes nothing, so only the first
         // min(NG, nlive) groups are formed and summed (one pass of row + 3 threads when one or two blocks were live)

@@ -232,18 +232,18 @@ __global__ __launch_bounds__(FUSED_BLOCK) void solve_fused_kernel(FusedArgs A, D
     __shared__ int s_wtrace[16][2];  // (per wave: start / end of the round-0 statistics)
     if (threadIdx.x < 24) s_trace[threadIdx.x] = 0;
 #endif
-    extern __shared__ __attribute__((aligned(16))) float s_dyn[];  // [8R] mean groups, [T*KROW] step rows, then the tail's staging
+    extern __shared__ __attribute__((aligned(16))) float s_dyn[];  // FusedLds: [8R] mean groups, [T*KROW] step rows, then the tail's staging
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, b = blockIdx.x, G = gridDim.x;
     const long long t0 = wall_clock64();
     bool timed_out = false;
 
     // ---- stage the wave-uniform per-step inputs (like rollout_cost_kernel)
     float4* s_mean4 = reinterpret_cast<float4*>(s_dyn);
-    float* s_ktab = s_dyn + 8 * d.R;
+    float* s_ktab = s_dyn + FusedLds::ktab(d.R);
     for (int f = tid; f < 4 * d.R; f += FUSED_BLOCK) {
         const float m = f < d.row ? A.mean[f] : 0.0f;
         s_dyn[f] = m;
-        s_dyn[4 * d.R + f] = 0.0f;
+        s_dyn[FusedLds::zeros(d.R) + f] = 0.0f;
         if (b == 0 && f < d.row) A.mean_used[f] = m;
     }
     for (int f = tid; f < d.T * M::KROW; f += FUSED_BLOCK) s_ktab[f] = ctx.ref[f];
@@ -499,9 +499,9 @@ __global__ __launch_bounds__(FUSED_BLOCK) void solve_fused_kernel(FusedArgs A, D
     }
 
     // ---- block 0: fold the blocks' rows in ascending order, then the tail of the solve
-    float* s_act = s_dyn + 8 * d.R + d.T * M::KROW;  // [row]
-    float* s_sum = s_act + d.row;                     // [4 + row]
-    float* s_yp = s_sum + MPPI_SUMMARY_HEAD + d.row;  // filter staging
+    float* s_act = s_dyn + 8 * d.R + d.T * M::KROW;   // [row]        (FusedLds::act)
+    float* s_sum = s_act + d.row;                     // [4 + row]    (FusedLds::sum)
+    float* s_yp = s_sum + MPPI_SUMMARY_HEAD + d.row;  // filter staging (FusedLds::yp)
     const bool rescale = small && !cmin_known;  // the blocks' exponents are relative to their own minima
     float cmin = cref;
     if (rescale) {  // finalize_tail's combine of shard summaries, applied to the blocks: f_b = exp((-cref_b)/lambda - max)

@@ -18,6 +18,7 @@
 //   capi_colored.hip   temporally correlated noise: the setting, its per-column table, the filtered draws (mppi_sample.hpp)
 // Kernel headers, one per stage.  A kernel that is not a template is defined in the one unit that launches it.
 //   mppi_common.hpp    Dims, GenCtx, wave reductions
+//   mppi_lds.hpp       the dynamic-LDS layout of every kernel that carves one up: offsets for the kernel, the total for its launch site
 //   mppi_cells.hpp     the tagged 8-byte cell: how blocks of one launch and peer devices hand values over (search, fused, exchange)
 //   mppi_sample.hpp    step 1: the noise stream (gen_noise4), sample_kernel, posterior draws; opt-in: sample_colored_kernel,
 //                      posterior_colored_kernel (mppi_colored.hpp: the scalar rule of the AR(1) filter)
@@ -150,18 +151,28 @@ struct MppiSolver {
 
     // per-solve sequence counters (the noise's solve index is core.gen.solve_idx)
     struct Seq {
-        int min_slot = 0;     // which of the two min_key slots the last rollout wrote (toggled per rollout)
         unsigned fused = 0;   // tag of the last single-launch solve's cells (fused.cells)
         unsigned brent = 0;   // probe-tag base of the next Brent search (search.brent_cells)
         unsigned round1 = 0;  // tag of the last ESSPS round-1 cells (search.round1_cells)
         unsigned p2p = 0;     // tag of the last peer-to-peer exchange (xchg.p2p_local)
     } seq;
 
+    // The minimum cost of the last rollout as an ordered key, double-buffered: a rollout accumulates (atomicMin) into the slot
+    // the rollout before it reset and resets the other one for the next -> no memset between solves.
+    struct MinKey {
+        DevBuf<unsigned> slots;        // two
+        int idx = 0;                   // which of them the last rollout wrote
+        struct Rollout { unsigned* accumulate; unsigned* reset_next; };
+        const unsigned* cur() const { return slots.p + idx; }
+        unsigned* cur_rw() { return slots.p + idx; }  // (refresh_min_key: the costs were replaced, not rolled out)
+        Rollout begin_rollout() { idx ^= 1; return {slots.p + idx, slots.p + (idx ^ 1)}; }
+        void cancel_rollout() { idx ^= 1; }  // a rollout that was begun and then not launched
+    } min_key;
+
     // noise, costs and the state / mean the solve starts from
     struct Core {
         DevBuf<float4> noise;
         DevBuf<float> costs;
-        DevBuf<unsigned> min_key;      // two slots, toggled per rollout (no memset between solves)
         DevBuf<float> x0;              // owned copy of the state ...
         const float* x0_cur = nullptr; // ... or a borrowed device pointer (mppi_bind_state)
         DevBuf<float> x0_used;         // the state the last rollout started from (snapshot taken by the rollout kernel)

@@ -2,6 +2,7 @@
 // Part of the MPPI.forward() hot path for gfx950; see mppi_handle.hpp for the map of the files.
 #pragma once
 #include "mppi_action_cost.hpp"
+#include "mppi_lds.hpp"
 #include "mppi_sample.hpp"
 
 namespace mppi {
@@ -340,10 +341,11 @@ __global__ __launch_bounds__(BLOCK) void rollout_cost_wave_kernel(const float* _
     using M = ModelT<MODEL, FAST>;
     using K = typename M::K;
     constexpr int DS = M::DS, DC = M::DC, NW = BLOCK / WAVE;
-    extern __shared__ __attribute__((aligned(16))) float s_dyn[];  // per wave: U[row4] then S[(T+1)*DS]
+    extern __shared__ __attribute__((aligned(16))) float s_dyn[];  // WaveRolloutLds, per wave: U[row4] then S[(T+1)*DS]
+    static_assert(NW == WaveRolloutLds::WAVES, "the launch site sizes the LDS for the block's waves");
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int row4 = 4 * d.R;
-    float* sU = s_dyn + (size_t)wid * (row4 + (d.T + 1) * DS);
+    const int row4 = WaveRolloutLds::s(d.R);
+    float* sU = s_dyn + (size_t)wid * (row4 + (d.T + 1) * DS);  // (WaveRolloutLds::per_wave)
     float* sS = sU + row4;
     if (blockIdx.x == 0 && threadIdx.x == 0) *next_min_key = 0xFFFFFFFFu;
     float wmin = INFINITY;

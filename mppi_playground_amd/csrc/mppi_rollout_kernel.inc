@@ -42,8 +42,8 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void MPPI_ROLLOUT_KERNEL(c
         s_min_key = min_key;
         if (stamps != nullptr && blockIdx.x == 0) stamps[0] = wall_clock64();
     }
-    // [4*R] mean groups, [4*R] zeros (samples that do not inherit the mean), (with the control-cost term: [4*R] g = mean *
-    // inv_covariance,) then [T*KROW] step rows
+    // RolloutLds: [4*R] mean groups, [4*R] zeros (samples that do not inherit the mean), (with the control-cost term: [4*R] g =
+    // mean * inv_covariance,) then [T*KROW] step rows
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     // One extra block (the last) when the PREVIOUS solve left its state sequence pending (option "lazy_state_seq"): the
     // batch-1 rollout of that solution (mppi.py:448-449) from the inputs finalize_kernel left in b1_in — T dependent steps
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void MPPI_ROLLOUT_KERNEL(c
     if (b1_state_out != nullptr && blockIdx.x == gridDim.x - 1) {
         for (int i = threadIdx.x; i < d.row + M::DS; i += BLOCK) s_dyn[i] = b1_in[i];
         __syncthreads();
-        batch1_rollout<MODEL, FAST>(ctx, s_dyn + d.row, s_dyn, d.T, b1_state_out);
+        batch1_rollout<MODEL, FAST>(ctx, s_dyn + RolloutLds::rider_x0(d.row), s_dyn, d.T, b1_state_out);
         if (stamps != nullptr && threadIdx.x == 0) (void)atomicMax(stamps + 1, (unsigned long long)wall_clock64());
         return;
     }
@@ -62,11 +62,11 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void MPPI_ROLLOUT_KERNEL(c
     // re-rolls of this solve's samples (get_top_samples, _state_seq_batch) read the snapshot
     if (blockIdx.x == 0 && threadIdx.x < M::DS) x0_used[threadIdx.x] = x0[threadIdx.x];
     float4* s_mean4 = reinterpret_cast<float4*>(s_dyn);
-    float* s_ktab = s_dyn + (MPPI_ROLLOUT_AC ? 12 : 8) * d.R;
+    float* s_ktab = s_dyn + RolloutLds::ktab(d.R, MPPI_ROLLOUT_AC != 0);
     for (int f = threadIdx.x; f < 4 * d.R; f += BLOCK) {
         const float m = f < d.row ? mean[f] : 0.0f;
         s_dyn[f] = m;
-        s_dyn[4 * d.R + f] = 0.0f;
+        s_dyn[RolloutLds::zeros(d.R) + f] = 0.0f;
 #if MPPI_ROLLOUT_AC
         {   // row 0 of the inverse covariance is zero (action_cost_inv); zeros past the row
             float g = 0.0f;
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void MPPI_ROLLOUT_KERNEL(c
                 const float sg = ac.sigtab ? ac.sigtab[f] : d.sigma[f % M::DC];
                 g = action_cost_g(m, action_cost_inv(f / M::DC, sg));
             }
-            s_dyn[8 * d.R + f] = g;
+            s_dyn[RolloutLds::g(d.R) + f] = g;
         }
 #endif
         // the mean this solve samples around outlives the warm-start update (get_top_samples re-rolls with it)
@@ -95,9 +95,9 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void MPPI_ROLLOUT_KERNEL(c
         const bool inherit = (d.sample_offset + i) < d.inherit_count;
         const float4* np = noise + tile * d.R * 64 + lane;
         bool bad = false;
-        const float4* mp = inherit ? s_mean4 : s_mean4 + d.R;
+        const float4* mp = inherit ? s_mean4 : s_mean4 + d.R;  // (RolloutLds::zeros, in float4 groups)
 #if MPPI_ROLLOUT_AC
-        total = lane_cost<MODEL, FAST, GEN, UC, true>(np, gi, gen, mp, s_ktab, x0, d, ctx, s_mean4 + 2 * d.R, &s_kappa);
+        total = lane_cost<MODEL, FAST, GEN, UC, true>(np, gi, gen, mp, s_ktab, x0, d, ctx, s_mean4 + 2 * d.R /* RolloutLds::g, in float4 groups */, &s_kappa);
 #else
         total = lane_cost<MODEL, FAST, GEN, UC>(np, gi, gen, mp, s_ktab, x0, d, ctx);
 #endif

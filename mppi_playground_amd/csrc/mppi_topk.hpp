@@ -304,11 +304,6 @@ constexpr int TOPK_DIRECT_MAX = 4096;
 #else
 #define TK_TRACE(i) do { } while (0)
 #endif
-constexpr int TOPK_PREGEN_MAX_R = 32;  // rows of up to 32 float4 groups (T <= 64 at two controls): 32 KiB of LDS
-// dynamic LDS of topk_rollout_kernel: the two mean rows [8R floats] + (unsorted candidates, regen mode) the block's noise
-inline size_t topk_rollout_lds(int R, bool sorted, bool gen_noise) {
-    return sizeof(float) * 8 * (size_t)R + (!sorted && gen_noise && R <= TOPK_PREGEN_MAX_R ? sizeof(float4) * 64 * (size_t)R : 0);
-}
 template <int MODEL, int FAST, bool SORTED>
 __global__ __launch_bounds__(TOPK_MAX) void topk_rollout_kernel(const unsigned long long* __restrict__ cand, int k,
                                                                 const float* __restrict__ costs, int n_direct,
@@ -324,7 +319,7 @@ __global__ __launch_bounds__(TOPK_MAX) void topk_rollout_kernel(const unsigned l
     constexpr int DS = ModelT<MODEL, FAST>::DS;
     __shared__ __attribute__((aligned(16))) unsigned long long s_key[SORTED ? 1 : TOPK_MAX];
     __shared__ __attribute__((aligned(16))) unsigned long long s_key2[SORTED ? 1 : TOPK_MAX];  // the sort's second buffer; the select's histogram before that
-    // [4R] the mean row the solve sampled around (zeros past the row), [4R] zeros (samples beyond the exploration split): the
+    // TopkLds: [4R] the mean row the solve sampled around (zeros past the row), [4R] zeros (samples beyond the exploration split): the
     // re-roll reads its mean groups from here (rollout_states_noise)
     extern __shared__ __attribute__((aligned(16))) float s_mrow[];
     __shared__ float s_x0[DS];
@@ -337,14 +332,14 @@ __global__ __launch_bounds__(TOPK_MAX) void topk_rollout_kernel(const unsigned l
     const auto stage_inputs = [&]() {
         for (int f = threadIdx.x; f < 4 * d.R; f += blockDim.x) {
             s_mrow[f] = f < d.row ? mean[f] : 0.0f;
-            s_mrow[4 * d.R + f] = 0.0f;
+            s_mrow[TopkLds::zeros(d.R) + f] = 0.0f;
         }
         if (threadIdx.x < DS) s_x0[threadIdx.x] = x0[threadIdx.x];
     };
     if (SORTED) { stage_inputs(); __syncthreads(); }
-    // (dynamic LDS behind the mean rows: the block's noise, see below; sized by topk_rollout_lds())
-    const bool pregen = !SORTED && gen_noise && d.R <= TOPK_PREGEN_MAX_R;
-    float4* s_noise = reinterpret_cast<float4*>(s_mrow + 8 * d.R);
+    // (dynamic LDS behind the mean rows: the block's noise, see below)
+    const bool pregen = TopkLds::pregen(d.R, SORTED, gen_noise);
+    float4* s_noise = reinterpret_cast<float4*>(s_mrow + TopkLds::noise(d.R));
     if (hist && blockIdx.x == 0) {  // leave the select state clean for the next call
         for (int b = threadIdx.x; b < 3 * TOPK_BINS; b += blockDim.x) hist[b] = 0u;
         if (threadIdx.x < 2) counters[threadIdx.x] = 0u;
@@ -536,7 +531,7 @@ __global__ __launch_bounds__(TOPK_MAX) void topk_rollout_kernel(const unsigned l
         s_key[tid] = v[0];
         __syncthreads();
         q = blockIdx.x * WAVE + tid;
-        // The fifteen waves that do not re-roll generate the block's noise first (regen mode, rows of <= TOPK_PREGEN_MAX_R
+        // The fifteen waves that do not re-roll generate the block's noise first (regen mode, rows of <= TopkLds::PREGEN_MAX_R
         // groups): group g of candidate 64 b + lane by wave g mod 16, into LDS as [g][lane] — the serial chain of the
         // re-roll is then the model's steps alone (the Philox + Box-Muller of a group is about as long as its two steps).
         if (pregen) {
@@ -561,7 +556,7 @@ __global__ __launch_bounds__(TOPK_MAX) void topk_rollout_kernel(const unsigned l
     const int64_t i = (int64_t)gi - d.sample_offset;  // local index: only meaningful when the tiles are read
     const float4* np = noise + ((i >> 6) * d.R) * 64 + (i & 63);
     float* out = states + (int64_t)q * (d.T + 1) * DS;
-    const float4* mp = reinterpret_cast<const float4*>(s_mrow) + (inherit ? 0 : d.R);
+    const float4* mp = reinterpret_cast<const float4*>(s_mrow) + (inherit ? 0 : d.R);  // (TopkLds::zeros, in float4 groups)
     const auto roll = [&](auto loadg) {
         const bool bad = rollout_states_noise<MODEL, FAST>(s_x0, d, ctx, out, mp, loadg);
         if constexpr (FAST != 0 && !EntryGeneral<ModelT<MODEL, FAST>>::value) {  // (a lane that left a fast path: the library-math walk)
