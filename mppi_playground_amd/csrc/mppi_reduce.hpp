@@ -49,6 +49,9 @@ __global__ __launch_bounds__(BLOCK) MPPI_REDUCE_ATTR void weights_reduce_kernel(
     constexpr int NW = BLOCK / WAVE;
     constexpr int CHG = NW * GPW;  // float4 groups per column chunk
     constexpr int TPW = 8;
+    // box_muller's three-instruction u1 (philox.hpp) keeps a constant in a vector register; the instantiation that sits at 72
+    // VGPRs, the last count with seven waves per SIMD, draws with the four-instruction form, the same bits
+    constexpr bool U1_FMA = CHAINS != 2 || REM;
     constexpr int RP = 8;  // accumulators combined per pass of the cross-lane sum (round 5: 8, was 32 — 33 KB of LDS for a
                            // tile used once after the loop held the kernel at three waves per SIMD)
     __shared__ float s_red[NW][RP][WAVE + 1];
@@ -160,18 +163,18 @@ __global__ __launch_bounds__(BLOCK) MPPI_REDUCE_ATTR void weights_reduce_kernel(
                     const auto quad = [&](int m0) {
                         float4 n4[4];
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) n4[k] = noise_group<true>(np, r0 + wid + NW * (m0 + k), gi, gen, d);
+                        for (int k = 0; k < 4; ++k) n4[k] = noise_group<true, U1_FMA>(np, r0 + wid + NW * (m0 + k), gi, gen, d);
 #pragma unroll
                         for (int k = 0; k < 4; ++k) accumulate(m0 + k, n4[k]);
                     };
                     const auto pair = [&](int m0) {
                         float4 n4[2];
 #pragma unroll
-                        for (int k = 0; k < 2; ++k) n4[k] = noise_group<true>(np, r0 + wid + NW * (m0 + k), gi, gen, d);
+                        for (int k = 0; k < 2; ++k) n4[k] = noise_group<true, U1_FMA>(np, r0 + wid + NW * (m0 + k), gi, gen, d);
 #pragma unroll
                         for (int k = 0; k < 2; ++k) accumulate(m0 + k, n4[k]);
                     };
-                    const auto single = [&](int m) { accumulate(m, noise_group<true>(np, r0 + wid + NW * m, gi, gen, d)); };
+                    const auto single = [&](int m) { accumulate(m, noise_group<true, U1_FMA>(np, r0 + wid + NW * m, gi, gen, d)); };
                     static_assert(GPW == 8, "the cases below are written for eight groups per wave");
                     // (independent `if`s, no else branches: every region updates its accumulators in place or not at all —
                     // nested if / else chains made the compiler add a second block of 28 accumulator moves per tile)
@@ -201,7 +204,7 @@ __global__ __launch_bounds__(BLOCK) MPPI_REDUCE_ATTR void weights_reduce_kernel(
                 const bool mine = REM && (rem == 1 ? ((int)tile & 3) == wid : rem == 2 ? ((int)tile & 1) == (wid >> 1) : wid < rem);
                 if (mine) {  // wave-uniform
                     const int g = NW * full + (rem == 1 ? 0 : rem == 2 ? (wid & 1) : wid);
-                    accumulate4(accx, g, noise_group<GEN>(np, r0 + g, gi, gen, d));
+                    accumulate4(accx, g, noise_group<GEN, U1_FMA>(np, r0 + g, gi, gen, d));
                 }
             }
         }

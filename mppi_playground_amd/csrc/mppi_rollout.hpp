@@ -80,6 +80,10 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
     ModelCtx ctx = ctx_in;
     if constexpr (FAST != 0 && EntryGeneral<M>::value) M::pin_hot(ctx);
     KeyPins pins{gen.seed_lo, gen.seed_hi, gen.seed_lo + 0x9E3779B9u};
+    // The three-instruction u1 of box_muller (philox.hpp) keeps 2^-24 in a vector register.  The rollout kernels of the goal
+    // zone sit at 80 VGPRs, the last count with six waves per SIMD, and the learned model's control-cost kernel at 96, the
+    // last with five: with it they lose a wave (82 / 97), so these models draw with the four-instruction form, the same bits.
+    constexpr bool U1_FMA = MODEL != MPPI_MODEL_GOALZONE && MODEL != MPPI_MODEL_MLP41;
     if (GEN) asm volatile("" : "+v"(pins.k0v), "+v"(pins.k1v), "+v"(pins.k0w));
     float s[DS], pu[DC], pl[DC];
 #pragma unroll
@@ -102,7 +106,7 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
     }
     CostSum<exact_cost_sum(MODEL)> acc;  // sum of the stage costs (mppi.py:333): exactly rounded (racing: sequential fp32)
     K knext = M::load_k(ktab, 0);
-    float4 e = noise_group<GEN>(np, 0, gi, gen, d, &pins);
+    float4 e = noise_group<GEN, U1_FMA>(np, 0, gi, gen, d, &pins);
     float4 m4 = mean4[0];
     {   // info["prev_action"] of step 0 is U[:, 0] itself (mppi.py:299-301)
         const float e0[4] = {e.x, e.y, e.z, e.w}, m0[4] = {m4.x, m4.y, m4.z, m4.w};
@@ -194,7 +198,7 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
             const int end = half == 0 ? full >> 1 : full;
             for (; r < end; ++r) {
                 const int rn = min(r + 1, d.R - 1);
-                const float4 en = noise_group<GEN>(np, rn, gi, gen, d, &pins);  // independent chain, interleaved with the steps
+                const float4 en = noise_group<GEN, U1_FMA>(np, rn, gi, gen, d, &pins);  // independent chain, interleaved with the steps
                 const float4 m4n = mean4[rn];
                 const float ev[4] = {e.x, e.y, e.z, e.w};
                 const float mv[4] = {m4.x, m4.y, m4.z, m4.w};
@@ -215,7 +219,7 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
         // Tiles: loads return in order (one vmcnt), so the first map gather consumed after a noise load also
         // waits for that load.  Keep two groups in flight and issue the load of group r+2 at the very END of
         // iteration r (pinned by a fake dependency on the iteration's result): it then has most of iteration r+1 to arrive.
-        float4 e1 = noise_group<GEN>(np, min(1, d.R - 1), gi, gen, d);
+        float4 e1 = noise_group<GEN, U1_FMA>(np, min(1, d.R - 1), gi, gen, d);
         for (int r = 0; r < full; ++r) {
             const float4 m4n = mean4[min(r + 1, d.R - 1)];
             const float ev[4] = {e.x, e.y, e.z, e.w};

@@ -31,15 +31,16 @@ __device__ __forceinline__ float4 noise_from_bits(const u32x4& x, int r, const D
     return make_float4(z[0], z[1], z[2], z[3]);
 }
 struct KeyPins { uint32_t k0v, k1v, k0w; };  // key words in VGPRs (philox4x32_10: rounds 0 and 1), pinned once by a caller with a hot loop
-template <bool WIDE = false>
+// U1_FMA: which of box_muller's two equal forms of u1 the caller's registers afford (philox.hpp).
+template <bool WIDE = false, bool U1_FMA = true>
 __device__ __forceinline__ float4 gen_noise4(uint64_t gi, int r, const GenCtx& g, const Dims& d,
                                              const float* __restrict__ sig_cols = nullptr, const KeyPins* pins = nullptr) {
     const u32x4 x = philox4x32_10((uint32_t)gi, (uint32_t)(gi >> 32), (uint32_t)r, g.solve_idx, g.seed_lo, g.seed_hi,
                                   pins ? pins->k0v : g.seed_lo, pins ? pins->k1v : g.seed_hi,
                                   pins ? pins->k0w : g.seed_lo + 0x9E3779B9u);
     float z[4];
-    box_muller(x.x, x.y, z[0], z[1]);
-    box_muller(x.z, x.w, z[2], z[3]);
+    box_muller<U1_FMA>(x.x, x.y, z[0], z[1]);
+    box_muller<U1_FMA>(x.z, x.w, z[2], z[3]);
     // columns past the row length (row % 4 != 0) carry unused values: no consumer reads them
 #pragma unroll
     for (int j = 0; j < 4; ++j) z[j] *= WIDE ? sig_cols[4 * r + j] : d.sigma[ctrl_index(j, d.dc)];
@@ -193,10 +194,10 @@ __global__ __launch_bounds__(BLOCK) void posterior_colored_kernel(const float* _
 }
 
 // One float4 group of a lane's noise row: from the tiles (GEN=false) or regenerated (GEN=true).
-template <bool GEN>
+template <bool GEN, bool U1_FMA = true>
 __device__ __forceinline__ float4 noise_group(const float4* __restrict__ np, int r, uint64_t gi, const GenCtx& g,
                                               const Dims& d, const KeyPins* pins = nullptr) {
-    if (GEN) return gen_noise4(gi, r, g, d, nullptr, pins);
+    if (GEN) return gen_noise4<false, U1_FMA>(gi, r, g, d, nullptr, pins);
     return np[(int64_t)r * 64];
 }
 

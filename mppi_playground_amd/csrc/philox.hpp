@@ -49,10 +49,30 @@ __device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_
 // Box-Muller on (a, b): u1 = ((a>>8)+1) * 2^-24 in (0,1], u2 = (b>>9) * 2^-23 in [0,1).
 // Hardware transcendentals: v_log_f32 (log2), v_sqrt_f32, v_sin_f32 / v_cos_f32.  The latter take their argument in
 // REVOLUTIONS and are periodic in 1, so the angle needs neither the 2*pi multiply nor a conversion: the 23 bits of u2 are
-// the mantissa of a float in [1, 2) (one shift + one OR), and cos(2 pi (1 + u2)) = cos(2 pi u2).
+// the mantissa of a float in [1, 2), and cos(2 pi (1 + u2)) = cos(2 pi u2).
+//
+// 1 + u2 = 0x3f800000 | (b>>9) is formed as the low word of (0x7f:b) >> 9, ONE funnel shift (v_alignbit_b32) instead of a
+// shift and an OR: 0x7f << 23 is the exponent field of 1.0 and the shift leaves bits 23..31 of the low word to it alone
+// (every b >> 9 is compared on the device by tests/test_gpu_box_muller_identity.py).
+//
+// u1 = ((a>>8)+1) * 2^-24 is shift, add, convert, multiply; fma((float)(a>>8), 2^-24, 2^-24) is the same number to the bit
+// in three instructions: n = a>>8 < 2^24 converts exactly, the scale is a power of two and (n+1) * 2^-24 is representable
+// (n+1 needs more than 24 bits only when it IS 2^24), so the single rounding of the FMA rounds nothing (every a >> 8 is
+// compared on the device by the same test).  The two forms are equal; which one a caller takes (U1_FMA) is a matter of
+// registers only: 2^-24 is no inline constant and the FMA needs it twice — the compiler holds it in a vector register
+// (v_fmamk_f32), which a kernel that sits on a register step pays with a wave per SIMD (trajectory_cost names the models
+// whose rollout kernels do; held in a scalar register instead it costs the racing rollout kernel its eighth wave,
+// profiles/r19_noise_chain.md).
+__device__ __forceinline__ float bm_angle(uint32_t b) { return __uint_as_float(__builtin_amdgcn_alignbit(0x7fu, b, 9)); }
+__device__ __forceinline__ float bm_u1_fma(uint32_t a) {
+    return __builtin_fmaf((float)(a >> 8), 1.0f / 16777216.0f, 1.0f / 16777216.0f);
+}
+__device__ __forceinline__ float bm_u1_mul(uint32_t a) { return (float)((a >> 8) + 1u) * (1.0f / 16777216.0f); }
+
+template <bool U1_FMA = true>
 __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-    const float u1 = (float)((a >> 8) + 1u) * (1.0f / 16777216.0f);
-    const float rev = __uint_as_float(0x3f800000u | (b >> 9));  // 1 + u2
+    const float u1 = U1_FMA ? bm_u1_fma(a) : bm_u1_mul(a);
+    const float rev = bm_angle(b);  // 1 + u2, in revolutions
     const float rad = __builtin_amdgcn_sqrtf(-1.38629436112f * __builtin_amdgcn_logf(u1));  // -2 ln2 log2(u1)
     z0 = rad * __builtin_amdgcn_cosf(rev);
     z1 = rad * __builtin_amdgcn_sinf(rev);

@@ -4,14 +4,15 @@
 #include <cstdio>
 #include <stdint.h>
 
-enum { FMA, MAD_U64, MUL_LO, MUL_HI, MUL_U24, LOG, SIN, SQRT, RCP, EXP, CVT, BITOP3, MED3, PHILOX_ROUND, N_MODES };
+enum { FMA, MAD_U64, MUL_LO, MUL_HI, MUL_U24, LOG, SIN, SQRT, RCP, EXP, CVT, BITOP3, MED3, MAD_U24, LSHL_ADD, ALIGNBIT, PHILOX_ROUND, N_MODES };
 static const char* kNames[N_MODES] = {"v_fma_f32", "v_mad_u64_u32", "v_mul_lo_u32", "v_mul_hi_u32", "v_mul_u32_u24",
                                       "v_log_f32", "v_sin_f32", "v_sqrt_f32", "v_rcp_f32", "v_exp_f32",
-                                      "v_cvt_f32_u32", "v_bitop3_b32", "v_med3_f32", "philox round (2 mad_u64 + 2 bitop3)"};
-static const int kInstPerIter[N_MODES] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 4};
+                                      "v_cvt_f32_u32", "v_bitop3_b32", "v_med3_f32", "v_mad_u32_u24", "v_lshl_add_u32",
+                                      "v_alignbit_b32", "philox round (2 mad_u64 + 2 bitop3)"};
+static const int kInstPerIter[N_MODES] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 4};
 
 template <int MODE>
-__global__ __launch_bounds__(256) void k(float* out, float a, float b, uint32_t m, int iters) {
+__global__ __launch_bounds__(256) void k(float* out, float a, float b, uint32_t m, int iters, uint32_t sh) {
     float x[8];
     uint32_t u[8], w[8];
     for (int i = 0; i < 8; ++i) {
@@ -38,6 +39,11 @@ __global__ __launch_bounds__(256) void k(float* out, float a, float b, uint32_t 
             if (MODE == CVT) { x[i] = (float)u[i]; u[i] = __float_as_uint(x[i]); }
             if (MODE == BITOP3) u[i] = __builtin_amdgcn_bitop3_b32(u[i], w[i], m, 0x96);
             if (MODE == MED3) x[i] = __builtin_amdgcn_fmed3f(x[i], a, b);
+            // the padded-map index both ways (occ_lookup_pad: bx * stride + by against (bx << shift) + by; stride and
+            // shift are kernel arguments there, hence scalar operands) and the funnel shift of box_muller's angle
+            if (MODE == MAD_U24) u[i] = __umul24(u[i], m) + w[i];
+            if (MODE == LSHL_ADD) u[i] = (u[i] << sh) + w[i];
+            if (MODE == ALIGNBIT) u[i] = __builtin_amdgcn_alignbit(w[i], u[i], 9);
             if (MODE == PHILOX_ROUND) {
                 const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)u[i];
                 const uint64_t p1 = (uint64_t)0xCD9E8D57u * (uint64_t)w[i];
@@ -57,7 +63,7 @@ static void run(float* d, hipEvent_t e0, hipEvent_t e1, double& fma_ms) {
     float ms = 0;
     for (int rep = 0; rep < 2; ++rep) {
         hipEventRecord(e0);
-        hipLaunchKernelGGL(k<MODE>, dim3(blocks), dim3(256), 0, 0, d, 1.0001f, 0.5f, 0xD2511F53u, iters);
+        hipLaunchKernelGGL(k<MODE>, dim3(blocks), dim3(256), 0, 0, d, 1.0001f, 0.5f, 0xD2511F53u, iters, 7u);
         hipEventRecord(e1);
         hipEventSynchronize(e1);
         hipEventElapsedTime(&ms, e0, e1);
