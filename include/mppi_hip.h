@@ -61,7 +61,8 @@ enum {
     MPPI_MODEL_MJCARTPOLE = 5,  /* example/mujoco_cartpole.py:20-81 (continuous force, masspole = 1) */
     MPPI_MODEL_GOALZONE = 6,    /* src/envs/goal_in_danger_zone.py:113-156 (7-state unicycle + circle) */
     MPPI_MODEL_MLP41 = 7,       /* learned dynamics: a small MLP, 4 states, 1 control (mppi_set_mlp)  */
-    MPPI_MODEL_MLP42 = 8        /* the same with 2 controls                                           */
+    MPPI_MODEL_MLP42 = 8,       /* the same with 2 controls                                           */
+    MPPI_MODEL_NAV2D_DISCS = 9  /* MPPI_MODEL_NAV2D + up to MPPI_MAX_DISCS moving disc obstacles (mppi_set_discs) */
 };
 
 /* Racing parameter vector (mppi_set_model_params), racing_env.py:37-42,341-370, racing.py:41-46 */
@@ -71,6 +72,7 @@ enum { MPPI_RP_AMIN = 0, MPPI_RP_AMAX, MPPI_RP_SMIN, MPPI_RP_SMAX, MPPI_RP_L, MP
 /* Navigation2D parameter vector, navigation_2d.py:54-72,218-279 */
 enum { MPPI_NP_VMIN = 0, MPPI_NP_VMAX, MPPI_NP_WMIN, MPPI_NP_WMAX, MPPI_NP_DT, MPPI_NP_XLO, MPPI_NP_XHI,
        MPPI_NP_YLO, MPPI_NP_YHI, MPPI_NP_GX, MPPI_NP_GY, MPPI_NP_QO, MPPI_NP_COUNT };
+#define MPPI_MAX_DISCS 8 /* moving discs per horizon step of MPPI_MODEL_NAV2D_DISCS (same MPPI_NP_* parameters as nav2d) */
 
 /* Goal-in-danger-zone parameter vector, goal_in_danger_zone.py:78-87,113-156 */
 enum { MPPI_GP_VMIN = 0, MPPI_GP_VMAX, MPPI_GP_WMIN, MPPI_GP_WMAX, MPPI_GP_DT, MPPI_GP_GX, MPPI_GP_GY, MPPI_GP_CX,
@@ -110,7 +112,7 @@ typedef struct MppiConfig {
 const char* mppi_version(void);
 /* Integer version of THIS header's function signatures; bindings compare it with the constant they were written
  * against and refuse a stale library (a changed argument list would otherwise be called with shifted arguments). */
-#define MPPI_ABI_VERSION 14
+#define MPPI_ABI_VERSION 15
 int mppi_abi_version(void);
 /* Number of visible HIP devices (0 => the product cannot run; callers must fail loudly). */
 int mppi_device_count(void);
@@ -191,6 +193,29 @@ int mppi_set_reference(mppi_handle_t h, const float* ref_host, int rows, void* s
  * take these models (MPPI_E_INVALID: it has no handle to take the table from). */
 int mppi_set_mlp(mppi_handle_t h, const float* table_host, int n_floats, int hidden_layers, int activation, int residual,
                  void* stream);
+/* Moving obstacles for MPPI_MODEL_NAV2D_DISCS (dynamics, parameters and maps of MPPI_MODEL_NAV2D): the predicted discs as a
+ * table with one row per horizon step, discs [rows][n][4] = {cx, cy, r2, w}: centre, SQUARED radius (formed by the caller)
+ * and penalty of disc j at step t; rows >= T, 0 <= n <= MPPI_MAX_DISCS.  Stage cost of step t, on the state (x, y, .) the
+ * step starts from (info["t"] = t reads row t), in fp32:
+ *     base = nav2d's cost (goal distance + QO * occupancy, the same lookups)
+ *     pen = 0; for j = 0..n-1 (in this order): dx = x - cx, dy = y - cy; d2 = dx*dx + dy*dy; pen = pen + (d2 <= r2 ? w : 0)
+ *     cost = base + pen
+ * At option "math" = 0 every operation rounds on its own (two products and one add); the fast levels form
+ * d2 = fma(dx, dx, dy*dy).  Overlapping discs add up; with n = 0 or no disc hit the cost is nav2d's bit for bit.
+ * The TERMINAL cost reads row T-1, not a row T: the reference evaluates its terminal cost with the stale info["t"] = T-1
+ * (mppi.py:318-328), the rule the racing model's reference row follows too.  A predictor that wants the discs of the
+ * moment the last state is reached has no row for it.
+ * mppi_set_discs pads n -> 8 (unused slots: r2 = -1, w = 0) into a buffer the handle owns, in stream order and without a
+ * host wait: a host table (on_device = 0) is checked (finite, w >= 0), staged and copied like mppi_set_reference's window;
+ * a device table (on_device != 0) is padded by one small kernel, so an obstacle predictor on the device never meets the
+ * host — and is NOT checked (that would need a host wait): the predictor keeps its values finite and w >= 0.  A horizon whose
+ * T rows (128 B each) do not fit in a block's LDS is refused at solve time (MPPI_E_INVALID).  The buffer grows (blocking, set-up path) only when `rows` exceeds every earlier call's.  The table may be replaced
+ * before every solve; re-rolls of an earlier solve (get_top_samples, a lazily completed state sequence) need the dynamics
+ * only and are not affected.  MPPI_E_INVALID for another model's handle, n outside 0..8, rows < 1; solves without a table
+ * or with fewer rows than the horizon return MPPI_E_STATE.  mppi_clone_state copies the table.
+ * mppi_get_discs returns the PADDED table [rows][8][4] (out may be NULL to query rows and n only); host copies synchronise. */
+int mppi_set_discs(mppi_handle_t h, const float* discs, int rows, int n, int on_device, void* stream);
+int mppi_get_discs(mppi_handle_t h, float* out, int* rows_out, int* n_out, int on_device, void* stream);
 
 /* The racing control tick without the host (example/racing.py:73-81,161-218,221-266).
  *   mppi_set_center_path  `env.racing_center_path` [n][3] = (x, y, yaw) and the constants of

@@ -341,6 +341,11 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
         CLONE(model.mlp);
         dm.ctx.ref = dm.mlp; dm.ctx.ref_rows = sm.ctx.ref_rows;
     }
+    if (sm.discs && sm.ctx.ref) {  // moving discs: the padded table; rows ride in ref_rows, the count in tan_small (copied with ctx)
+        if (dm.discs.n != sm.discs.n) HIP_TRY(dst, dm.discs.alloc(sm.discs.n));
+        CLONE(model.discs);
+        dm.ctx.ref = dm.discs; dm.ctx.ref_rows = sm.ctx.ref_rows;
+    }
     if (sm.center_n) {
         HIP_TRY(dst, dm.center8.alloc(sm.center8.n));
         HIP_TRY(dst, dm.win_dind.alloc(sm.win_dind.n));

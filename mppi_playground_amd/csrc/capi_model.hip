@@ -1,5 +1,6 @@
 // capi_model.hip — C ABI (include/mppi_hip.h): model parameters, maps, the reference and its device-resident window,
 // env.step and grid lookups on the device.
+#include <algorithm>
 #include <cmath>
 
 #include "mppi_handle.hpp"
@@ -15,7 +16,7 @@ void refresh_pad(mppi_handle_t h, hipStream_t s) {
     h->model.ctx.pad_stride = 0;
     const int model = h->cfg.model;
     const bool racing = model == MPPI_MODEL_RACING;
-    if (!racing && model != MPPI_MODEL_NAV2D) return;
+    if (!racing && !is_nav2d(model)) return;
     if (!h->model.params_set || !h->model.map_cells[0] || (racing && !h->model.map_cells[1])) return;
     const MapView &a = h->model.ctx.maps[0], &b = h->model.ctx.maps[1];
     if (racing && (a.nx != b.nx || a.ny != b.ny || a.cell != b.cell || a.ox != b.ox || a.oy != b.oy)) return;
@@ -65,6 +66,29 @@ int reserve_ref(mppi_handle_t h, int rows) {
     return MPPI_OK;
 }
 
+// value `f` of the padded table [rows][8][4] from the caller's [rows][n][4]: slots past n hold {0, 0, r2 = -1, w = 0}
+__host__ __device__ inline float disc_padded(const float* discs, int n, size_t f) {
+    const size_t t = f / DISC_ROW;
+    const int j = (int)(f % DISC_ROW) / DISC_FLOATS, c = (int)(f % DISC_FLOATS);
+    if (j < n) return discs[(t * n + j) * DISC_FLOATS + c];
+    return c == 2 ? DISC_PAD_R2 : c == 3 ? DISC_PAD_W : 0.0f;
+}
+
+// mppi_set_discs from a device table: the padding, in stream order (one thread per value of the padded table)
+__global__ __launch_bounds__(BLOCK) void disc_rows_kernel(const float* __restrict__ discs, int rows, int n, float* __restrict__ out) {
+    const size_t f = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (f < (size_t)rows * DISC_ROW) out[f] = disc_padded(discs, n, f);
+}
+
+// make sure h->model.discs holds `rows` rows (blocking reallocation: set-up path; at least the horizon from the start)
+static int reserve_discs(mppi_handle_t h, int rows) {
+    if ((size_t)rows * DISC_ROW <= h->model.discs.n) return MPPI_OK;
+    if (h->model.discs) HIP_TRY(h, hipDeviceSynchronize());
+    h->model.ctx.ref = nullptr; h->model.ctx.ref_rows = 0;
+    HIP_TRY(h, h->model.discs.alloc((size_t)DISC_ROW * (size_t)std::max(rows, h->d.T)));
+    return MPPI_OK;
+}
+
 }  // namespace mppi
 
 extern "C" {
@@ -81,7 +105,7 @@ int mppi_set_model_params(mppi_handle_t h, const float* p, int n) {
         const float w = std::fmax(std::fabs(p[MPPI_GP_WMIN]), std::fabs(p[MPPI_GP_WMAX]));
         h->model.ctx.wrap_safe = (w * std::fabs(p[MPPI_GP_DT]) < 3.0f) ? 1 : 0;
     }
-    if (h->cfg.model == MPPI_MODEL_NAV2D) {
+    if (is_nav2d(h->cfg.model)) {
         h->model.ctx.u_in_bounds = (um[0] >= p[MPPI_NP_VMIN] && uM[0] <= p[MPPI_NP_VMAX] && um[1] >= p[MPPI_NP_WMIN] &&
                               uM[1] <= p[MPPI_NP_WMAX]) ? 1 : 0;
         const float w = std::fmax(std::fabs(p[MPPI_NP_WMIN]), std::fabs(p[MPPI_NP_WMAX]));
@@ -175,6 +199,7 @@ int mppi_download_map(mppi_handle_t h, int slot, uint8_t* cells_host, int* nx, i
 int mppi_set_reference(mppi_handle_t h, const float* ref, int rows, void* stream) {
     if (!h || !ref || rows < 1) return fail(h, MPPI_E_INVALID, "bad reference");
     if (is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "a learned-dynamics handle has no reference window");
+    if (h->cfg.model == MPPI_MODEL_NAV2D_DISCS) return fail(h, MPPI_E_INVALID, "a moving-disc handle has no reference window");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = reserve_ref(h, rows)) return rc;
     float* st = nullptr; hipEvent_t ev = nullptr;
@@ -213,6 +238,49 @@ int mppi_set_mlp(mppi_handle_t h, const float* table, int n_floats, int hidden_l
     h->model.ctx.ref = h->model.mlp;
     h->model.ctx.ref_rows = (hidden_layers == 2 ? MLP_TWO_LAYERS : 0) | (activation == MPPI_MLP_TANH ? MLP_TANH : 0) |
                             (residual ? MLP_RESIDUAL : 0);
+    return MPPI_OK;
+}
+
+int mppi_set_discs(mppi_handle_t h, const float* discs, int rows, int n, int on_device, void* stream) {
+    if (!h) return MPPI_E_INVALID;
+    if (h->cfg.model != MPPI_MODEL_NAV2D_DISCS) return fail(h, MPPI_E_INVALID, "the disc table belongs to the moving-disc model");
+    if (rows < 1 || n < 0 || n > MPPI_MAX_DISCS || (n > 0 && !discs))
+        return fail(h, MPPI_E_INVALID, "disc table: rows >= 1 and 0 <= n <= 8 discs per row");
+    const size_t in_floats = (size_t)rows * n * DISC_FLOATS, floats = (size_t)rows * DISC_ROW;
+    if (!on_device)
+        for (size_t i = 0; i < in_floats; ++i)
+            if (!std::isfinite(discs[i]) || (i % DISC_FLOATS == 3 && discs[i] < 0.0f))
+                return fail(h, MPPI_E_INVALID, "disc table: every value must be finite and every penalty >= 0");
+    if (int rc = reserve_discs(h, rows)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (on_device) {
+        hipLaunchKernelGGL(disc_rows_kernel, dim3((unsigned)((floats + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, discs, rows, n,
+                           h->model.discs.p);
+        HIP_TRY(h, hipGetLastError());
+    } else {
+        float* st = nullptr; hipEvent_t ev = nullptr;
+        if (int rc = stage_slot(h, floats, &st, &ev)) return rc;
+        for (size_t f = 0; f < floats; ++f) st[f] = disc_padded(discs, n, f);
+        HIP_TRY(h, hipMemcpyAsync(h->model.discs, st, sizeof(float) * floats, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipEventRecord(ev, s));
+    }
+    h->model.ctx.ref = h->model.discs;
+    h->model.ctx.ref_rows = rows;
+    h->model.ctx.tan_small = n;  // (disc_count: mppi_models.hpp)
+    return MPPI_OK;
+}
+
+int mppi_get_discs(mppi_handle_t h, float* out, int* rows_out, int* n_out, int on_device, void* stream) {
+    if (!h) return MPPI_E_INVALID;
+    if (h->cfg.model != MPPI_MODEL_NAV2D_DISCS) return fail(h, MPPI_E_INVALID, "the disc table belongs to the moving-disc model");
+    if (!h->model.ctx.ref) return fail(h, MPPI_E_STATE, "no disc table: call mppi_set_discs first");
+    if (rows_out) *rows_out = h->model.ctx.ref_rows;
+    if (n_out) *n_out = disc_count(h->model.ctx);
+    if (!out) return MPPI_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipMemcpyAsync(out, h->model.discs, sizeof(float) * DISC_ROW * (size_t)h->model.ctx.ref_rows,
+                              on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    if (!on_device) HIP_TRY(h, hipStreamSynchronize(s));
     return MPPI_OK;
 }
 
@@ -272,6 +340,7 @@ int mppi_get_path_index(mppi_handle_t h, int32_t* cind_out_host, void* stream) {
 int mppi_get_reference(mppi_handle_t h, float* ref_out, int rows, int on_device, void* stream) {
     if (!h || !ref_out || rows < 1) return fail(h, MPPI_E_INVALID, "bad get_reference arguments");
     if (is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "a learned-dynamics handle has no reference window");
+    if (h->cfg.model == MPPI_MODEL_NAV2D_DISCS) return fail(h, MPPI_E_INVALID, "a moving-disc handle has no reference window");
     if (!h->model.ctx.ref || rows > h->model.ctx.ref_rows) return fail(h, MPPI_E_STATE, "no reference window of that many rows");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipMemcpy2DAsync(ref_out, 4 * sizeof(float), h->model.ref, 8 * sizeof(float), 4 * sizeof(float), (size_t)rows,
@@ -310,6 +379,7 @@ int mppi_model_step(int model, const float* params_host, int n_params, const flo
     case MPPI_MODEL_RACING: CALL_STEP(MPPI_MODEL_RACING); break;
     case MPPI_MODEL_MJCARTPOLE: CALL_STEP(MPPI_MODEL_MJCARTPOLE); break;
     case MPPI_MODEL_GOALZONE: CALL_STEP(MPPI_MODEL_GOALZONE); break;
+    case MPPI_MODEL_NAV2D_DISCS: CALL_STEP(MPPI_MODEL_NAV2D_DISCS); break;  // (nav2d's dynamics: the discs are cost only)
     }
 #undef CALL_STEP
     return hipGetLastError() == hipSuccess ? MPPI_OK : MPPI_E_HIP;

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "../../include/mppi_hip.h"
+#include "mppi_discs.hpp"
 
 #if defined(__HIPCC__)
 #define MPPI_HD __host__ __device__ __forceinline__
@@ -62,6 +63,12 @@ constexpr int MLP_TWO_LAYERS = 1, MLP_TANH = 2, MLP_RESIDUAL = 4;
 constexpr int mlp_table_floats(int dc) {
     return MPPI_MLP_HIDDEN * (4 + dc) + MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN * MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN + 4 * MPPI_MLP_HIDDEN + 4;
 }
+
+// The moving-disc model (MPPI_MODEL_NAV2D_DISCS; mppi_set_discs): the padded table [rows][8][4] is ModelCtx::ref and
+// ref_rows its row count (the solve checks it against the horizon); the launch-uniform number of discs per row rides in
+// ModelCtx::tan_small, a racing flag this model has no other use for, so the kernels' argument struct is what it was.
+static_assert(DISC_ROW == 4 * MPPI_MAX_DISCS, "mppi_discs.hpp spells the row of MPPI_MAX_DISCS discs");
+MPPI_HD int disc_count(const ModelCtx& c) { return c.tan_small; }
 
 // Host-side plan of the padded grid.  The models clamp positions to [xlo, xhi] x [ylo, yhi]; if every index
 // round(p/cell + origin) reachable under that clamp lies in [0, nx] x [0, ny], the lookup needs no bounds test.

@@ -450,6 +450,26 @@ struct Model<MPPI_MODEL_NAV2D, FAST> {  // src/envs/navigation_2d.py:218-279
     }
 };
 
+// nav2d with up to MPPI_MAX_DISCS moving disc obstacles (include/mppi_hip.h, mppi_set_discs, states the rule; mppi_discs.hpp
+// is the arithmetic).  Dynamics, entry and the static-map cost are Model<NAV2D>'s.  The step-constant table holds one row
+// of 8 discs per horizon step; K is only the address of row t in the block's LDS copy (one register across the step, not
+// 8 x 4 floats): cost() reads the discs of its row there, each one 16-byte read at a wave-uniform address, and stops at the
+// launch-uniform count (disc_count).  The terminal cost reads row T-1 like every user of the table (trajectory_cost).
+template <bool FAST>
+struct Model<MPPI_MODEL_NAV2D_DISCS, FAST> : Model<MPPI_MODEL_NAV2D, FAST> {
+    using Base = Model<MPPI_MODEL_NAV2D, FAST>;
+    struct K { const float* row; };
+    static constexpr int KROW = DISC_ROW;
+    static_assert(KROW == 4 * MPPI_MAX_DISCS, "one row = MPPI_MAX_DISCS discs of {cx, cy, r2, w}");
+    static MPPI_HD K load_k(const float* tab, int t) { return K{tab + KROW * t}; }  // tab = ctx.ref or its LDS copy
+    static MPPI_HD float cost(const ModelCtx& c, const K& k, const float* s, const float* u, const float* pu, bool& bad,
+                              bool general = false) {
+        const float base = Base::cost(c, NoStepConst{}, s, u, pu, bad, general);
+        const float pen = disc_row_penalty<FAST>(k.row, disc_count(c), s[0], s[1]);
+        return base + pen;
+    }
+};
+
 template <bool FAST>
 struct Model<MPPI_MODEL_RACING, FAST> {  // src/envs/racing_env.py:327-372, example/racing.py:110-159
     static constexpr int DS = 4, DC = 2;

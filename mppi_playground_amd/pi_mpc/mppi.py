@@ -582,6 +582,12 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                 self._h.call("mppi_set_mlp", tab.ctypes.data_as(C.c_void_p), int(tab.size), int(mlp["hidden_layers"]),
                              _capi.MLP_ACTIVATIONS[mlp["activation"]], int(bool(mlp["residual"])), self._stream())
                 self._h.mlp_key = key
+        discs = spec.get("discs")
+        if discs is not None:  # moving discs: the predicted table travels again whenever its owner bumped the version
+            key = (id(self._cost_owner), discs["version"])
+            if getattr(self._h, "discs_key", None) != key:  # (kept on the handle, like the weight table's)
+                self._put_discs(discs["table"])
+                self._h.discs_key = key
         for slot, grid in enumerate(spec.get("maps", ())):
             key = (id(grid.cells), grid.version)
             if self._uploaded.get(slot) != key:
@@ -592,6 +598,26 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             r = np.ascontiguousarray(ref, dtype=np.float32)
             self._h.call("mppi_set_reference", r.ctypes.data_as(C.c_void_p), r.shape[0], self._stream())
             self._ref_uploaded = ref
+
+    def _put_discs(self, table) -> None:
+        """The moving-disc table [rows, n, 4] = {cx, cy, r2, w} per horizon step -> the handle (mppi_set_discs, on the
+        current stream, no host wait): a tensor on the solver's device is padded there, anything else goes through the
+        pinned staging ring."""
+        shape = tuple(table.shape)
+        if len(shape) != 3 or shape[2] != 4:
+            raise ValueError(f"disc table: expected [rows, n, 4], got {list(shape)}")
+        if shape[1] > _capi.MAX_DISCS:
+            raise ValueError(f"disc table: {shape[1]} discs per step, the fused model takes at most {_capi.MAX_DISCS}")
+        if shape[0] < self._horizon:
+            raise ValueError(f"disc table: {shape[0]} rows for a horizon of {self._horizon} (one row per step)")
+        if torch.is_tensor(table) and table.is_cuda and table.device == self._device:
+            dev = table.detach().to(self._dtype).contiguous()
+            self._h.call("mppi_set_discs", _ptr(dev) if dev.numel() else None, shape[0], shape[1], 1, self._stream())
+            self._discs_keep = dev  # (alive until the next table: the padding kernel reads it in stream order)
+        else:
+            host = np.ascontiguousarray(table.detach().cpu().numpy() if torch.is_tensor(table) else table, dtype=np.float32)
+            self._h.call("mppi_set_discs", host.ctypes.data_as(C.c_void_p) if host.size else None, shape[0], shape[1], 0,
+                         self._stream())
 
     def _put_map(self, slot: int, grid) -> None:
         """Occupancy grid -> device slot: rasterised on the device from the integer recipe when the map
