@@ -62,7 +62,8 @@ enum {
     MPPI_MODEL_GOALZONE = 6,    /* src/envs/goal_in_danger_zone.py:113-156 (7-state unicycle + circle) */
     MPPI_MODEL_MLP41 = 7,       /* learned dynamics: a small MLP, 4 states, 1 control (mppi_set_mlp)  */
     MPPI_MODEL_MLP42 = 8,       /* the same with 2 controls                                           */
-    MPPI_MODEL_NAV2D_DISCS = 9  /* MPPI_MODEL_NAV2D + up to MPPI_MAX_DISCS moving disc obstacles (mppi_set_discs) */
+    MPPI_MODEL_NAV2D_DISCS = 9, /* MPPI_MODEL_NAV2D + up to MPPI_MAX_DISCS moving disc obstacles (mppi_set_discs) */
+    MPPI_MODEL_RACING_DISCS = 10 /* MPPI_MODEL_RACING + up to MPPI_MAX_DISCS moving disc obstacles: opponent cars (mppi_set_discs) */
 };
 
 /* Racing parameter vector (mppi_set_model_params), racing_env.py:37-42,341-370, racing.py:41-46 */
@@ -72,7 +73,8 @@ enum { MPPI_RP_AMIN = 0, MPPI_RP_AMAX, MPPI_RP_SMIN, MPPI_RP_SMAX, MPPI_RP_L, MP
 /* Navigation2D parameter vector, navigation_2d.py:54-72,218-279 */
 enum { MPPI_NP_VMIN = 0, MPPI_NP_VMAX, MPPI_NP_WMIN, MPPI_NP_WMAX, MPPI_NP_DT, MPPI_NP_XLO, MPPI_NP_XHI,
        MPPI_NP_YLO, MPPI_NP_YHI, MPPI_NP_GX, MPPI_NP_GY, MPPI_NP_QO, MPPI_NP_COUNT };
-#define MPPI_MAX_DISCS 8 /* moving discs per horizon step of MPPI_MODEL_NAV2D_DISCS (same MPPI_NP_* parameters as nav2d) */
+#define MPPI_MAX_DISCS 8 /* moving discs per horizon step of MPPI_MODEL_NAV2D_DISCS / MPPI_MODEL_RACING_DISCS (the MPPI_NP_* /
+                          * MPPI_RP_* parameters of nav2d / racing) */
 
 /* Goal-in-danger-zone parameter vector, goal_in_danger_zone.py:78-87,113-156 */
 enum { MPPI_GP_VMIN = 0, MPPI_GP_VMAX, MPPI_GP_WMIN, MPPI_GP_WMAX, MPPI_GP_DT, MPPI_GP_GX, MPPI_GP_GY, MPPI_GP_CX,
@@ -112,7 +114,7 @@ typedef struct MppiConfig {
 const char* mppi_version(void);
 /* Integer version of THIS header's function signatures; bindings compare it with the constant they were written
  * against and refuse a stale library (a changed argument list would otherwise be called with shifted arguments). */
-#define MPPI_ABI_VERSION 15
+#define MPPI_ABI_VERSION 16
 int mppi_abi_version(void);
 /* Number of visible HIP devices (0 => the product cannot run; callers must fail loudly). */
 int mppi_device_count(void);
@@ -213,7 +215,22 @@ int mppi_set_mlp(mppi_handle_t h, const float* table_host, int n_floats, int hid
  * before every solve; re-rolls of an earlier solve (get_top_samples, a lazily completed state sequence) need the dynamics
  * only and are not affected.  MPPI_E_INVALID for another model's handle, n outside 0..8, rows < 1; solves without a table
  * or with fewer rows than the horizon return MPPI_E_STATE.  mppi_clone_state copies the table.
- * mppi_get_discs returns the PADDED table [rows][8][4] (out may be NULL to query rows and n only); host copies synchronise. */
+ * mppi_get_discs returns the PADDED table [rows][8][4] (out may be NULL to query rows and n only); host copies synchronise.
+ *
+ * MPPI_MODEL_RACING_DISCS (dynamics, parameters, maps, entry rules and reference window of MPPI_MODEL_RACING): the same
+ * table, the same calls and the same row rule on top of racing's cost — opponent cars as discs.  In fp32:
+ *     base = racing's cost ((path + velocity + obstacle + input), racing's operations in racing's order)
+ *     pen  = as above, on the state (x, y, ., .) the step starts from
+ *     cost = base + pen                     (added last; the stage costs are summed sequentially in fp32, like racing's)
+ * With n = 0 or no disc hit the cost is racing's bit for bit.  Reference row and disc row of step t are row t of their
+ * tables, the terminal cost reads row T-1 of both.  The handle keeps ONE step table [rows][40]: floats 0-7 of a row are the
+ * reference row (x, y, yaw, v, sin yaw, cos yaw, 0, 0), floats 8-39 its eight padded discs.  It has two writers, each of which
+ * writes its floats only, in stream order, in either order and as often as it likes without the other (the racing tick
+ * rewrites the window every tick while the discs may stay): mppi_set_reference / mppi_ref_window write floats 0-7,
+ * mppi_set_discs floats 8-39; mppi_get_reference and mppi_get_discs return each part as for the single-part models.  A solve
+ * returns MPPI_E_STATE until BOTH parts are present with at least T rows each.  mppi_clone_state copies both parts and the
+ * count.  On a plain MPPI_MODEL_RACING handle mppi_set_discs / mppi_get_discs stay MPPI_E_INVALID and the window keeps its
+ * [rows][8] layout, byte for byte.  mppi_model_step takes the id and runs racing's dynamics (the discs are cost only). */
 int mppi_set_discs(mppi_handle_t h, const float* discs, int rows, int n, int on_device, void* stream);
 int mppi_get_discs(mppi_handle_t h, float* out, int* rows_out, int* n_out, int on_device, void* stream);
 

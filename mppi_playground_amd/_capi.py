@@ -16,10 +16,10 @@ MODEL_GENERIC = -1
 MAX_DIM_CONTROL = 4           # controls held by MppiConfig
 MAX_DIM_CONTROL_GENERIC = 64  # opaque callables: any dim_control up to this
 MODEL_IDS = {"pendulum": 0, "cartpole": 1, "mountaincar": 2, "nav2d": 3, "racing": 4, "mjcartpole": 5, "goalzone": 6,
-             "mlp41": 7, "mlp42": 8, "nav2d_discs": 9}
+             "mlp41": 7, "mlp42": 8, "nav2d_discs": 9, "racing_discs": 10}
 MODEL_DIMS = {"pendulum": (2, 1), "cartpole": (4, 1), "mountaincar": (2, 1), "nav2d": (3, 2), "racing": (4, 2),
               "mjcartpole": (4, 1), "goalzone": (7, 2), "mlp41": (4, 1), "mlp42": (4, 2),
-              "nav2d_discs": (3, 2)}
+              "nav2d_discs": (3, 2), "racing_discs": (4, 2)}
 MLP_HIDDEN = 32               # MPPI_MLP_HIDDEN
 MLP_ACTIVATIONS = {"relu": 0, "tanh": 1}  # MPPI_MLP_*
 MAX_DISCS = 8                 # MPPI_MAX_DISCS
@@ -28,7 +28,7 @@ LAMBDA_DEVICE = -1.0  # MPPI_LAMBDA_DEVICE: "the temperature a device-resident r
 AUTO_RULES = {None: 0, "ESSPS": 1, "LBPS": 2, "MPO": 3}  # MPPI_AUTO_*
 
 # every symbol include/mppi_hip.h declares
-ABI_VERSION = 15  # MPPI_ABI_VERSION of the header this binding was written against
+ABI_VERSION = 16  # MPPI_ABI_VERSION of the header this binding was written against
 
 SYMBOLS = [
     "mppi_version", "mppi_abi_version", "mppi_device_count", "mppi_last_error", "mppi_create", "mppi_destroy", "mppi_set_control_limits",

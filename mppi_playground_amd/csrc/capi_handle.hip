@@ -331,9 +331,11 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
         if (int rc = clone_buf(dst, dm.map_cells[slot].p, sm.map_cells[slot].p, (size_t)m.nx * m.ny)) return rc;
     }
     dm.ctx.ref = nullptr; dm.ctx.ref_rows = 0;
-    if (sm.ref) {
-        if (int rc = reserve_ref(dst, (int)(sm.ref.n / 8))) return rc;
+    dm.ref_part_rows = dm.disc_part_rows = 0;
+    if (sm.ref) {  // (racing with discs: the one step table carries both parts; the count rides in ctx.P, copied above)
+        if (int rc = reserve_ref(dst, (int)(sm.ref.n / (size_t)ref_stride(src->cfg.model)))) return rc;
         if (int rc = clone_buf(dst, dm.ref.p, sm.ref.p, sm.ref.n)) return rc;
+        dm.ref_part_rows = sm.ref_part_rows; dm.disc_part_rows = sm.disc_part_rows;
         if (sm.ctx.ref) { dm.ctx.ref = dm.ref; dm.ctx.ref_rows = sm.ctx.ref_rows; }
     }
     if (sm.mlp && sm.ctx.ref) {  // learned dynamics: the weight table, with the flags that ride in ref_rows

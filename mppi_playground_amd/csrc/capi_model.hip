@@ -15,7 +15,7 @@ void refresh_pad(mppi_handle_t h, hipStream_t s) {
     h->model.ctx.pad = nullptr;
     h->model.ctx.pad_stride = 0;
     const int model = h->cfg.model;
-    const bool racing = model == MPPI_MODEL_RACING;
+    const bool racing = is_racing_model(model);
     if (!racing && !is_nav2d(model)) return;
     if (!h->model.params_set || !h->model.map_cells[0] || (racing && !h->model.map_cells[1])) return;
     const MapView &a = h->model.ctx.maps[0], &b = h->model.ctx.maps[1];
@@ -58,12 +58,44 @@ static int upload_ints(mppi_handle_t h, const int32_t* src, size_t count, DevBuf
     return MPPI_OK;
 }
 
-// make sure h->model.ref holds `rows` rows (blocking reallocation: set-up path)
+// make sure h->model.ref holds `rows` rows of the model's stride (blocking reallocation: set-up path).  Racing with discs:
+// the table has a second writer, so a larger buffer starts from the old one's rows (the stride is the same: they keep
+// their places) and from at least the horizon, so that the racing tick's T + 1 window rows do not move a T-row disc part.
 int reserve_ref(mppi_handle_t h, int rows) {
-    if ((size_t)rows * 8 <= h->model.ref.n) return MPPI_OK;
+    const size_t stride = (size_t)ref_stride(h->cfg.model);
+    if ((size_t)rows * stride <= h->model.ref.n) return MPPI_OK;
     if (h->model.ref) HIP_TRY(h, hipDeviceSynchronize());
-    HIP_TRY(h, h->model.ref.alloc(8 * (size_t)rows));
+    if (h->cfg.model != MPPI_MODEL_RACING_DISCS) {
+        HIP_TRY(h, h->model.ref.alloc(stride * (size_t)rows));
+        return MPPI_OK;
+    }
+    DevBuf<float> grown;
+    const size_t floats = stride * (size_t)std::max(rows, h->d.T + 1);
+    HIP_TRY(h, grown.alloc(floats));
+    HIP_TRY(h, hipMemset(grown, 0, sizeof(float) * floats));
+    if (h->model.ref) HIP_TRY(h, hipMemcpy(grown, h->model.ref, sizeof(float) * h->model.ref.n, hipMemcpyDeviceToDevice));
+    h->model.ref = std::move(grown);  // (swaps: the old buffer is freed with `grown`)
+    if (h->model.ctx.ref) h->model.ctx.ref = h->model.ref;
     return MPPI_OK;
+}
+
+// Racing with discs: aim ctx.ref at the step table once BOTH of its parts have been written (check_ready names what is
+// missing until then); ref_rows = the rows both parts cover.
+static void publish_step_table(mppi_handle_t h) {
+    auto& m = h->model;
+    const int rows = std::min(m.ref_part_rows, m.disc_part_rows);
+    m.ctx.ref = rows > 0 ? m.ref.p : nullptr;
+    m.ctx.ref_rows = rows;
+}
+// the reference part of the model's table has `rows` rows now
+static void reference_written(mppi_handle_t h, int rows) {
+    if (h->cfg.model == MPPI_MODEL_RACING_DISCS) {
+        h->model.ref_part_rows = rows;
+        publish_step_table(h);
+        return;
+    }
+    h->model.ctx.ref = h->model.ref;
+    h->model.ctx.ref_rows = rows;
 }
 
 // value `f` of the padded table [rows][8][4] from the caller's [rows][n][4]: slots past n hold {0, 0, r2 = -1, w = 0}
@@ -78,6 +110,13 @@ __host__ __device__ inline float disc_padded(const float* discs, int n, size_t f
 __global__ __launch_bounds__(BLOCK) void disc_rows_kernel(const float* __restrict__ discs, int rows, int n, float* __restrict__ out) {
     const size_t f = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (f < (size_t)rows * DISC_ROW) out[f] = disc_padded(discs, n, f);
+}
+// the same into the disc part of a wider step row (racing with discs: `stride` floats per row, the discs from float `off`);
+// the other floats of the row are not touched
+__global__ __launch_bounds__(BLOCK) void disc_rows_strided_kernel(const float* __restrict__ discs, int rows, int n,
+                                                                  float* __restrict__ out, int stride, int off) {
+    const size_t f = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (f < (size_t)rows * DISC_ROW) out[(f / DISC_ROW) * (size_t)stride + off + f % DISC_ROW] = disc_padded(discs, n, f);
 }
 
 // make sure h->model.discs holds `rows` rows (blocking reallocation: set-up path; at least the horizon from the start)
@@ -111,7 +150,7 @@ int mppi_set_model_params(mppi_handle_t h, const float* p, int n) {
         const float w = std::fmax(std::fabs(p[MPPI_NP_WMIN]), std::fabs(p[MPPI_NP_WMAX]));
         h->model.ctx.wrap_safe = (w * std::fabs(p[MPPI_NP_DT]) < 3.0f) ? 1 : 0;
     }
-    if (h->cfg.model == MPPI_MODEL_RACING) {
+    if (is_racing_model(h->cfg.model)) {
         h->model.ctx.u_in_bounds = (um[0] >= p[MPPI_RP_AMIN] && uM[0] <= p[MPPI_RP_AMAX] && um[1] >= p[MPPI_RP_SMIN] &&
                               uM[1] <= p[MPPI_RP_SMAX]) ? 1 : 0;
         const float sm = std::fmax(std::fabs(p[MPPI_RP_SMIN]), std::fabs(p[MPPI_RP_SMAX]));
@@ -210,10 +249,13 @@ int mppi_set_reference(mppi_handle_t h, const float* ref, int rows, void* stream
         o[4] = sinf(o[2]); o[5] = cosf(o[2]);  // torch.sin/cos of the fp32 scalar, racing.py:127-139
         o[6] = o[7] = 0.0f;
     }
-    HIP_TRY(h, hipMemcpyAsync(h->model.ref, st, sizeof(float) * 8 * (size_t)rows, hipMemcpyHostToDevice, s));
+    const size_t pitch = sizeof(float) * (size_t)ref_stride(h->cfg.model);
+    if (pitch == sizeof(float) * 8)
+        HIP_TRY(h, hipMemcpyAsync(h->model.ref, st, sizeof(float) * 8 * (size_t)rows, hipMemcpyHostToDevice, s));
+    else  // racing with discs: floats 0-7 of every step row, the discs behind them stay
+        HIP_TRY(h, hipMemcpy2DAsync(h->model.ref, pitch, st, sizeof(float) * 8, sizeof(float) * 8, (size_t)rows, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(ev, s));
-    h->model.ctx.ref = h->model.ref;
-    h->model.ctx.ref_rows = rows;
+    reference_written(h, rows);
     return MPPI_OK;
 }
 
@@ -243,7 +285,7 @@ int mppi_set_mlp(mppi_handle_t h, const float* table, int n_floats, int hidden_l
 
 int mppi_set_discs(mppi_handle_t h, const float* discs, int rows, int n, int on_device, void* stream) {
     if (!h) return MPPI_E_INVALID;
-    if (h->cfg.model != MPPI_MODEL_NAV2D_DISCS) return fail(h, MPPI_E_INVALID, "the disc table belongs to the moving-disc model");
+    if (!has_discs(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the disc table belongs to the moving-disc models");
     if (rows < 1 || n < 0 || n > MPPI_MAX_DISCS || (n > 0 && !discs))
         return fail(h, MPPI_E_INVALID, "disc table: rows >= 1 and 0 <= n <= 8 discs per row");
     const size_t in_floats = (size_t)rows * n * DISC_FLOATS, floats = (size_t)rows * DISC_ROW;
@@ -251,8 +293,28 @@ int mppi_set_discs(mppi_handle_t h, const float* discs, int rows, int n, int on_
         for (size_t i = 0; i < in_floats; ++i)
             if (!std::isfinite(discs[i]) || (i % DISC_FLOATS == 3 && discs[i] < 0.0f))
                 return fail(h, MPPI_E_INVALID, "disc table: every value must be finite and every penalty >= 0");
-    if (int rc = reserve_discs(h, rows)) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (h->cfg.model == MPPI_MODEL_RACING_DISCS) {  // the disc part (floats 8-39) of the step table the reference window shares
+        if (int rc = reserve_ref(h, rows)) return rc;
+        const int stride = ref_stride(h->cfg.model), off = disc_offset(h->cfg.model);
+        if (on_device) {
+            hipLaunchKernelGGL(disc_rows_strided_kernel, dim3((unsigned)((floats + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, discs,
+                               rows, n, h->model.ref.p, stride, off);
+            HIP_TRY(h, hipGetLastError());
+        } else {
+            float* st = nullptr; hipEvent_t ev = nullptr;
+            if (int rc = stage_slot(h, floats, &st, &ev)) return rc;
+            for (size_t f = 0; f < floats; ++f) st[f] = disc_padded(discs, n, f);
+            HIP_TRY(h, hipMemcpy2DAsync(h->model.ref.p + off, sizeof(float) * stride, st, sizeof(float) * DISC_ROW,
+                                        sizeof(float) * DISC_ROW, (size_t)rows, hipMemcpyHostToDevice, s));
+            HIP_TRY(h, hipEventRecord(ev, s));
+        }
+        h->model.disc_part_rows = rows;
+        set_disc_count(h->model.ctx, h->cfg.model, n);
+        publish_step_table(h);
+        return MPPI_OK;
+    }
+    if (int rc = reserve_discs(h, rows)) return rc;
     if (on_device) {
         hipLaunchKernelGGL(disc_rows_kernel, dim3((unsigned)((floats + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, discs, rows, n,
                            h->model.discs.p);
@@ -266,18 +328,30 @@ int mppi_set_discs(mppi_handle_t h, const float* discs, int rows, int n, int on_
     }
     h->model.ctx.ref = h->model.discs;
     h->model.ctx.ref_rows = rows;
-    h->model.ctx.tan_small = n;  // (disc_count: mppi_models.hpp)
+    set_disc_count(h->model.ctx, h->cfg.model, n);  // (disc_count: mppi_models.hpp)
     return MPPI_OK;
 }
 
 int mppi_get_discs(mppi_handle_t h, float* out, int* rows_out, int* n_out, int on_device, void* stream) {
     if (!h) return MPPI_E_INVALID;
-    if (h->cfg.model != MPPI_MODEL_NAV2D_DISCS) return fail(h, MPPI_E_INVALID, "the disc table belongs to the moving-disc model");
+    if (!has_discs(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the disc table belongs to the moving-disc models");
+    hipStream_t s = (hipStream_t)stream;
+    if (h->cfg.model == MPPI_MODEL_RACING_DISCS) {
+        const int rows = h->model.disc_part_rows;
+        if (rows < 1) return fail(h, MPPI_E_STATE, "no disc table: call mppi_set_discs first");
+        if (rows_out) *rows_out = rows;
+        if (n_out) *n_out = disc_count(h->model.ctx, h->cfg.model);
+        if (!out) return MPPI_OK;
+        HIP_TRY(h, hipMemcpy2DAsync(out, sizeof(float) * DISC_ROW, h->model.ref.p + disc_offset(h->cfg.model),
+                                    sizeof(float) * ref_stride(h->cfg.model), sizeof(float) * DISC_ROW, (size_t)rows,
+                                    on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        if (!on_device) HIP_TRY(h, hipStreamSynchronize(s));
+        return MPPI_OK;
+    }
     if (!h->model.ctx.ref) return fail(h, MPPI_E_STATE, "no disc table: call mppi_set_discs first");
     if (rows_out) *rows_out = h->model.ctx.ref_rows;
     if (n_out) *n_out = disc_count(h->model.ctx);
     if (!out) return MPPI_OK;
-    hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipMemcpyAsync(out, h->model.discs, sizeof(float) * DISC_ROW * (size_t)h->model.ctx.ref_rows,
                               on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     if (!on_device) HIP_TRY(h, hipStreamSynchronize(s));
@@ -287,7 +361,7 @@ int mppi_get_discs(mppi_handle_t h, float* out, int* rows_out, int* n_out, int o
 int mppi_set_center_path(mppi_handle_t h, const float* path_host, int n, const int32_t* dind_host, int rows,
                          float v_target) {
     if (!h || !path_host || !dind_host || n < 1 || rows < 1) return fail(h, MPPI_E_INVALID, "bad centre path");
-    if (h->cfg.model != MPPI_MODEL_RACING) return fail(h, MPPI_E_INVALID, "the reference window belongs to the racing model");
+    if (!is_racing_model(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the reference window belongs to the racing models");
     if (rows < h->d.T) return fail(h, MPPI_E_INVALID, "window shorter than the horizon");
     for (int i = 0; i < rows; ++i)
         if (dind_host[i] < 0 || (i && dind_host[i] < dind_host[i - 1])) return fail(h, MPPI_E_INVALID, "window offsets must be >= 0 and non-decreasing");
@@ -312,12 +386,12 @@ int mppi_set_center_path(mppi_handle_t h, const float* path_host, int n, const i
 int mppi_ref_window(mppi_handle_t h, const float* state_dev, void* stream) {
     if (!h) return MPPI_E_INVALID;
     if (!h->model.center_n) return fail(h, MPPI_E_STATE, "mppi_ref_window before mppi_set_center_path");
-    const RefWindowCtx w{h->model.center8, h->model.win_dind, h->model.path_index, h->model.center_n, h->model.win_rows, h->model.win_v};
+    const RefWindowCtx w{h->model.center8, h->model.win_dind, h->model.path_index, h->model.center_n, h->model.win_rows, h->model.win_v,
+                         ref_stride(h->cfg.model)};
     hipLaunchKernelGGL(ref_window_kernel, dim3(1), dim3(REFWIN_BLOCK), 0, (hipStream_t)stream, w,
                        state_dev ? state_dev : h->core.x0_cur, h->model.ref);
     HIP_TRY(h, hipGetLastError());
-    h->model.ctx.ref = h->model.ref;
-    h->model.ctx.ref_rows = h->model.win_rows;
+    reference_written(h, h->model.win_rows);
     return MPPI_OK;
 }
 
@@ -341,9 +415,11 @@ int mppi_get_reference(mppi_handle_t h, float* ref_out, int rows, int on_device,
     if (!h || !ref_out || rows < 1) return fail(h, MPPI_E_INVALID, "bad get_reference arguments");
     if (is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "a learned-dynamics handle has no reference window");
     if (h->cfg.model == MPPI_MODEL_NAV2D_DISCS) return fail(h, MPPI_E_INVALID, "a moving-disc handle has no reference window");
-    if (!h->model.ctx.ref || rows > h->model.ctx.ref_rows) return fail(h, MPPI_E_STATE, "no reference window of that many rows");
+    const bool two_parts = h->cfg.model == MPPI_MODEL_RACING_DISCS;  // (the window may be there before the discs are)
+    if (two_parts ? rows > h->model.ref_part_rows : (!h->model.ctx.ref || rows > h->model.ctx.ref_rows))
+        return fail(h, MPPI_E_STATE, "no reference window of that many rows");
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipMemcpy2DAsync(ref_out, 4 * sizeof(float), h->model.ref, 8 * sizeof(float), 4 * sizeof(float), (size_t)rows,
+    HIP_TRY(h, hipMemcpy2DAsync(ref_out, 4 * sizeof(float), h->model.ref, sizeof(float) * ref_stride(h->cfg.model), 4 * sizeof(float), (size_t)rows,
                                 on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     if (!on_device) HIP_TRY(h, hipStreamSynchronize(s));
     return MPPI_OK;
@@ -380,6 +456,7 @@ int mppi_model_step(int model, const float* params_host, int n_params, const flo
     case MPPI_MODEL_MJCARTPOLE: CALL_STEP(MPPI_MODEL_MJCARTPOLE); break;
     case MPPI_MODEL_GOALZONE: CALL_STEP(MPPI_MODEL_GOALZONE); break;
     case MPPI_MODEL_NAV2D_DISCS: CALL_STEP(MPPI_MODEL_NAV2D_DISCS); break;  // (nav2d's dynamics: the discs are cost only)
+    case MPPI_MODEL_RACING_DISCS: CALL_STEP(MPPI_MODEL_RACING); break;      // (racing's dynamics, racing's kernel)
     }
 #undef CALL_STEP
     return hipGetLastError() == hipSuccess ? MPPI_OK : MPPI_E_HIP;

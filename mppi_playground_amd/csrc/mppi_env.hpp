@@ -40,10 +40,11 @@ struct RefWindowCtx {
     int32_t* cind;        // current path index (`racing_controller.current_path_index`)
     int32_t n, rows;
     float v_target;       // env.V_MAX
+    int32_t stride;       // floats per row of the table the window is written into (8; racing with discs: 40, floats 0-7 of a row)
 };
 constexpr int REFWIN_BLOCK = 1024;
 __global__ __launch_bounds__(REFWIN_BLOCK) void ref_window_kernel(RefWindowCtx w, const float* __restrict__ state,
-                                                                  float* __restrict__ ref_out /*[rows][8]*/) {
+                                                                  float* __restrict__ ref_out /*[rows][w.stride]*/) {
     __shared__ unsigned long long s_best[REFWIN_BLOCK / WAVE];
     __shared__ int s_ind;
     // everything that does not depend on the search is requested before it (the carried index, this thread's window
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(REFWIN_BLOCK) void ref_window_kernel(RefWindowCtx w
         float4 a = src[0];
         const float4 b = src[1];
         a.w = all_inside ? w.v_target : 0.0f;
-        float4* dst = reinterpret_cast<float4*>(ref_out + 8 * (int64_t)i);
+        float4* dst = reinterpret_cast<float4*>(ref_out + w.stride * (int64_t)i);
         dst[0] = a;
         dst[1] = b;
     }

@@ -191,7 +191,7 @@ __device__ __forceinline__ void batch1_rollout(const ModelCtx& ctx, const float*
 #pragma unroll
         for (int k = 0; k < DC; ++k) u[k] = s_act[t * DC + k];
     };
-    if constexpr (MODEL == MPPI_MODEL_RACING && FAST) {
+    if constexpr (is_racing_model(MODEL) && FAST) {
         if (T <= 63) {  // the serial part of the batch-1 rollout shrinks to the heading/speed recurrences
             if (threadIdx.x >= WAVE) return;
             ModelT<MODEL, FAST>::rollout_wave(ctx, s_x0, s_act, T, state_out);  // (any finite start: no library-math redo)

@@ -290,7 +290,9 @@ struct MppiSolver {
         bool params_set = false;
         DevBuf<uint8_t> map_cells[2];
         DevBuf<uint8_t> map_pad;       // padded (and, for racing, summed) grid of the FAST lookup
-        DevBuf<float> ref;             // [rows][8] reference window
+        DevBuf<float> ref;             // [rows][8] reference window; racing with discs: the step table [rows][40] (ref_stride)
+        int ref_part_rows = 0;         // racing with discs: rows of the table whose reference part (floats 0-7) is written ...
+        int disc_part_rows = 0;        // ... and whose disc part (floats 8-39) is; ctx.ref is set once both are (publish_step_table)
         DevBuf<float> discs;           // [rows][8][4] padded disc table of the moving-disc model (mppi_set_discs); ctx.ref points at it
         DevBuf<float> mlp;             // weight table of the learned-dynamics models (mppi_set_mlp); ctx.ref points at it
         // device-resident reference window (mppi_set_center_path / mppi_ref_window)
@@ -369,14 +371,17 @@ inline bool model_dims(int model, ModelDims& md) {
     case MPPI_MODEL_MLP41: md = {4, 1}; return true;
     case MPPI_MODEL_MLP42: md = {4, 2}; return true;
     case MPPI_MODEL_NAV2D_DISCS: md = {3, 2}; return true;
+    case MPPI_MODEL_RACING_DISCS: md = {4, 2}; return true;
     }
     return false;
 }
 // nav2d and its moving-disc variant: one set of dynamics, parameters, maps and host-checked preconditions
 inline bool is_nav2d(int model) { return model == MPPI_MODEL_NAV2D || model == MPPI_MODEL_NAV2D_DISCS; }
+// the models that carry a disc table (mppi_set_discs)
+inline bool has_discs(int model) { return model == MPPI_MODEL_NAV2D_DISCS || model == MPPI_MODEL_RACING_DISCS; }
 // parameters the dynamics of `model` read (the models without any take none)
 inline int model_param_count(int model) {
-    return model == MPPI_MODEL_RACING ? MPPI_RP_COUNT : is_nav2d(model) ? MPPI_NP_COUNT
+    return is_racing_model(model) ? MPPI_RP_COUNT : is_nav2d(model) ? MPPI_NP_COUNT
            : model == MPPI_MODEL_GOALZONE ? MPPI_GP_COUNT : model == MPPI_MODEL_MLP41 ? MPPI_MP_COUNT41
            : model == MPPI_MODEL_MLP42 ? MPPI_MP_COUNT42 : 0;
 }
@@ -465,7 +470,7 @@ inline bool use_fast(mppi_handle_t h) {
     if (is_nav2d(m))
         return c.maps[0].inv_cell != 0.0f && c.pad != nullptr && c.wrap_safe != 0 && c.u_in_bounds != 0;
     if (m == MPPI_MODEL_GOALZONE) return c.wrap_safe != 0 && c.u_in_bounds != 0;
-    if (m == MPPI_MODEL_RACING)
+    if (is_racing_model(m))
         return c.wrap_safe != 0 && c.u_in_bounds != 0 && c.maps[0].inv_cell != 0.0f && c.pad != nullptr && c.tan_small != 0 && c.inv_L != 0.0f;
     return true;
 }
@@ -495,6 +500,7 @@ inline int math_level(mppi_handle_t h) { return use_fast(h) ? (h->opt.math_fast 
         MPPI_DISPATCH_NOHW(MPPI_MODEL_MLP41, CALL)                                                    \
         MPPI_DISPATCH_NOHW(MPPI_MODEL_MLP42, CALL)                                                    \
         MPPI_DISPATCH_HW(MPPI_MODEL_NAV2D_DISCS, CALL)                                                \
+        MPPI_DISPATCH_HW(MPPI_MODEL_RACING_DISCS, CALL)                                               \
         }                                                                                             \
     } while (0)
 
@@ -502,19 +508,28 @@ inline int check_ready(mppi_handle_t h) {
     const int m = h->cfg.model;
     if (m == MPPI_MODEL_GENERIC)
         return fail(h, MPPI_E_INVALID, "generic model: dynamics/cost are host callables, this entry point is unavailable");
-    if ((is_nav2d(m) || m == MPPI_MODEL_RACING) && !h->model.map_cells[0])
+    if ((is_nav2d(m) || is_racing_model(m)) && !h->model.map_cells[0])
         return fail(h, MPPI_E_STATE, "obstacle map (slot 0) not uploaded");
-    if (m == MPPI_MODEL_RACING && !h->model.map_cells[1]) return fail(h, MPPI_E_STATE, "lane map (slot 1) not uploaded");
+    if (is_racing_model(m) && !h->model.map_cells[1]) return fail(h, MPPI_E_STATE, "lane map (slot 1) not uploaded");
     if (m == MPPI_MODEL_RACING && (!h->model.ctx.ref || h->model.ctx.ref_rows < h->d.T))
         return fail(h, MPPI_E_STATE, "reference path not set or shorter than the horizon");
+    // racing with discs: one step table, two writers (capi_model.hip); ctx.ref is aimed at it once BOTH parts are there
+    if (m == MPPI_MODEL_RACING_DISCS && h->model.ref_part_rows < h->d.T)
+        return fail(h, MPPI_E_STATE, "reference path not set or shorter than the horizon");
+    if (m == MPPI_MODEL_RACING_DISCS && h->model.disc_part_rows < 1)
+        return fail(h, MPPI_E_STATE, "no disc table: call mppi_set_discs first");
+    if (m == MPPI_MODEL_RACING_DISCS && h->model.disc_part_rows < h->d.T)
+        return fail(h, MPPI_E_STATE, "disc table has fewer rows than the horizon");
+    if (m == MPPI_MODEL_RACING_DISCS && (!h->model.ctx.ref || h->model.ctx.ref_rows < h->d.T))
+        return fail(h, MPPI_E_STATE, "step table of the racing-with-discs model is incomplete");
     if (is_mlp(m) && !h->model.ctx.ref) return fail(h, MPPI_E_STATE, "no weight table: call mppi_set_mlp first");
     if (m == MPPI_MODEL_NAV2D_DISCS && !h->model.ctx.ref) return fail(h, MPPI_E_STATE, "no disc table: call mppi_set_discs first");
     if (m == MPPI_MODEL_NAV2D_DISCS && h->model.ctx.ref_rows < h->d.T)
         return fail(h, MPPI_E_STATE, "disc table has fewer rows than the horizon");
     // the rollout kernels keep T rows of the table in LDS (mppi_lds.hpp): refuse a horizon whose rows do not fit next to the
     // mean groups here, by name, instead of as a failed launch
-    if (m == MPPI_MODEL_NAV2D_DISCS &&
-        sizeof(float) * RolloutLds::floats(h->d.R, h->d.T, h->d.row, DISC_ROW, true) > (size_t)h->lds_max)
+    if (has_discs(m) &&
+        sizeof(float) * RolloutLds::floats(h->d.R, h->d.T, h->d.row, disc_offset(m) + DISC_ROW, true) > (size_t)h->lds_max)
         return fail(h, MPPI_E_INVALID, "horizon too long for the moving-disc model: its table rows do not fit in LDS");
     return MPPI_OK;
 }

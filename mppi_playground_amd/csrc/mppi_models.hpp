@@ -68,7 +68,32 @@ constexpr int mlp_table_floats(int dc) {
 // ref_rows its row count (the solve checks it against the horizon); the launch-uniform number of discs per row rides in
 // ModelCtx::tan_small, a racing flag this model has no other use for, so the kernels' argument struct is what it was.
 static_assert(DISC_ROW == 4 * MPPI_MAX_DISCS, "mppi_discs.hpp spells the row of MPPI_MAX_DISCS discs");
-MPPI_HD int disc_count(const ModelCtx& c) { return c.tan_small; }
+// Racing with moving discs (MPPI_MODEL_RACING_DISCS): racing reads both `ref` and `tan_small` itself.  The table is still
+// ModelCtx::ref — ONE table of RACING_DISCS_KROW floats per step, the reference row in floats 0-7 and the eight padded discs
+// behind it (each disc 16-byte aligned) — and the count waits in the first P[] slot behind racing's parameters, as the BITS
+// of the integer (no conversion on the device; mppi_set_model_params writes MPPI_RP_COUNT values and leaves it alone).
+constexpr int RACING_REF_ROW = 8;                            // floats of a racing reference row
+constexpr int RACING_DISCS_KROW = RACING_REF_ROW + DISC_ROW;  // 40
+constexpr int RACING_DISCS_SLOT = MPPI_RP_COUNT;              // P[] slot of the disc count
+static_assert(RACING_DISCS_SLOT < MPPI_MAX_PARAMS, "the disc count needs a free parameter slot");
+static_assert(RACING_REF_ROW % 4 == 0 && RACING_DISCS_KROW % 4 == 0, "discs stay 16-byte aligned behind the reference row");
+constexpr bool is_racing_model(int model) { return model == MPPI_MODEL_RACING || model == MPPI_MODEL_RACING_DISCS; }
+// floats per step of the table ModelCtx::ref points at, for the models whose reference window the host entry points write
+constexpr int ref_stride(int model) { return model == MPPI_MODEL_RACING_DISCS ? RACING_DISCS_KROW : RACING_REF_ROW; }
+// first float of the discs inside a step row
+constexpr int disc_offset(int model) { return model == MPPI_MODEL_RACING_DISCS ? RACING_REF_ROW : 0; }
+// The number of discs per row: the one accessor both disc models go through (`model`: a constant where a kernel calls it)
+MPPI_HD int disc_count(const ModelCtx& c, int model = MPPI_MODEL_NAV2D_DISCS) {
+    if (model != MPPI_MODEL_RACING_DISCS) return c.tan_small;
+    int32_t n;
+    __builtin_memcpy(&n, &c.P[RACING_DISCS_SLOT], sizeof(n));
+    return n;
+}
+inline void set_disc_count(ModelCtx& c, int model, int n) {
+    if (model != MPPI_MODEL_RACING_DISCS) { c.tan_small = n; return; }
+    const int32_t v = n;
+    __builtin_memcpy(&c.P[RACING_DISCS_SLOT], &v, sizeof(v));
+}
 
 // Host-side plan of the padded grid.  The models clamp positions to [xlo, xhi] x [ylo, yhi]; if every index
 // round(p/cell + origin) reachable under that clamp lies in [0, nx] x [0, ny], the lookup needs no bounds test.
@@ -120,7 +145,7 @@ struct CostSum<true> {
 #ifndef MPPI_EXACT_SUM_RACING
 #define MPPI_EXACT_SUM_RACING 0  // (A/B knob of scripts/build_variant.sh: the double accumulator in the racing kernel too)
 #endif
-constexpr bool exact_cost_sum(int model) { return MPPI_EXACT_SUM_RACING || model != MPPI_MODEL_RACING; }
+constexpr bool exact_cost_sum(int model) { return MPPI_EXACT_SUM_RACING || !is_racing_model(model); }
 
 }  // namespace mppi
 

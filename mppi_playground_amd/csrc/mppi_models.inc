@@ -614,6 +614,31 @@ struct Model<MPPI_MODEL_RACING, FAST> {  // src/envs/racing_env.py:327-372, exam
     }
 };
 
+// Racing among up to MPPI_MAX_DISCS moving discs — opponent cars (include/mppi_hip.h, mppi_set_discs, states the rule;
+// mppi_discs.hpp is the arithmetic, exactly as nav2d's variant uses it).  Dynamics, entry rules, the pinned constants, the
+// wave-parallel batch-1 rollout and the whole of racing's cost are Model<RACING>'s.  The step-constant table holds ONE row
+// of RACING_DISCS_KROW = 40 floats per horizon step: racing's reference row in floats 0-7, the eight padded discs behind it
+// (mppi_models.hpp), so the kernels stage T * KROW contiguous floats of ctx.ref as they do for every model.  K carries
+// racing's five reference values and the address of the row's discs in the block's LDS copy; the penalty is added LAST, so
+// with no disc (disc_count = 0) or no hit the cost is racing's bit for bit.
+template <bool FAST>
+struct Model<MPPI_MODEL_RACING_DISCS, FAST> : Model<MPPI_MODEL_RACING, FAST> {
+    using Base = Model<MPPI_MODEL_RACING, FAST>;
+    struct K { typename Base::K ref; const float* discs; };
+    static constexpr int KROW = RACING_DISCS_KROW;
+    static_assert(KROW == RACING_REF_ROW + 4 * MPPI_MAX_DISCS, "one row = the reference row + MPPI_MAX_DISCS discs of {cx, cy, r2, w}");
+    static MPPI_HD K load_k(const float* tab, int t) {  // tab = ctx.ref or its LDS copy
+        const float* r = tab + KROW * t;
+        return K{typename Base::K{r[0], r[1], r[3], r[4], r[5]}, r + RACING_REF_ROW};
+    }
+    static MPPI_HD float cost(const ModelCtx& c, const K& k, const float* s, const float* u, const float* pu, bool& bad,
+                              bool general = false) {
+        const float base = Base::cost(c, k.ref, s, u, pu, bad, general);
+        const float pen = disc_row_penalty<FAST>(k.discs, disc_count(c, MPPI_MODEL_RACING_DISCS), s[0], s[1]);
+        return base + pen;
+    }
+};
+
 // Learned dynamics: a multi-layer perceptron whose weights are data (include/mppi_hip.h, mppi_set_mlp, states the
 // arithmetic; the table is ctx.ref, the flags ctx.ref_rows).  Every product-sum is written a * b + c: mppi::strict rounds
 // each operation on its own (the numpy restatement of tests/mlp_ref.py, bit for bit with relu), the fast namespaces may

@@ -126,7 +126,7 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
             for (int k = 0; k < DC; ++k) A = action_cost_accumulate(A, gv[k], u[k]);
         }
         float sn[DS], ss[DS];
-        if constexpr (MODEL == MPPI_MODEL_RACING) M::step(ctx, s, u, sn, ss, bad, UC, FAST != 0, VAR);
+        if constexpr (is_racing_model(MODEL)) M::step(ctx, s, u, sn, ss, bad, UC, FAST != 0, VAR);
         else M::step(ctx, s, u, sn, ss, bad, UC, FAST != 0);
         if constexpr (X0OUT) acc.add(M::cost(ctx, kcur, ss, u, pu, bad, t == 0));
         else acc.add(M::cost(ctx, kcur, ss, u, pu, bad));
@@ -188,7 +188,7 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
         // outer loop is unrolled).  Three copies keep the one loop: the library math (a second loop takes the goal zone's redo
         // from 80 to 82 VGPRs, a wave per SIMD), racing math = 1 (64 -> 65 VGPRs, a wave per SIMD) and the X0OUT copy, whose
         // `t == 0` test would stay inside the second loop.
-        constexpr bool DRAIN = FAST != 0 && !X0OUT && !(MODEL == MPPI_MODEL_RACING && FAST == 1);
+        constexpr bool DRAIN = FAST != 0 && !X0OUT && !(is_racing_model(MODEL) && FAST == 1);
         ROLLOUT_TRACE_LOOP_ENTRY();
         int r = 0;
 #pragma unroll
@@ -283,7 +283,7 @@ __device__ __forceinline__ float lane_cost(const float4* __restrict__ np, uint64
             return trajectory_cost<MODEL, FAST, GEN, UC, false, true, AC>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa);
     }
     // (racing, fast math: the unit wheel base of the reference is a launch-uniform branch around two copies of the loop)
-    if (MODEL == MPPI_MODEL_RACING && FAST != 0 && ctx.unit_L)
+    if (is_racing_model(MODEL) && FAST != 0 && ctx.unit_L)
         total = trajectory_cost<MODEL, FAST, GEN, UC, true, false, AC>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa);
     else
         total = trajectory_cost<MODEL, FAST, GEN, UC, false, false, AC>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa);

@@ -12,8 +12,9 @@ where `provider(owner)` returns the model's current inputs as plain host data:
      "mlp": {"table": float32[n], "hidden_layers": 1 | 2, "activation": "relu" | "tanh", "residual": bool, "version": int},
      "discs": {"table": float32 [rows, n, 4] = {cx, cy, r2, w} per horizon step (a torch tensor on the solver's device, or
                an ndarray), "version": int}}
-("mlp": the learned-dynamics models only; "discs": the moving-disc model "nav2d_discs" only, rows >= the horizon and
-n <= 8 or the solver raises ValueError; either table is uploaded again when its `version` changes.)
+("mlp": the learned-dynamics models only; "discs": the moving-disc models only — "nav2d_discs" (envs.MovingObstacleNav2DEnv)
+and "racing_discs" (envs.racing_opponents: opponent cars, next to racing's "ref_path" or device-built window) — rows >= the
+horizon and n <= 8 or the solver raises ValueError; either table is uploaded again when its `version` changes.)
 `owner` is the bound method's `__self__` (None for plain functions).  The solver calls the provider
 of the cost callable before every solve (the racing reference window changes every tick,
 example/racing.py:73-81) and re-uploads only what changed.

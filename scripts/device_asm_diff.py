@@ -4,8 +4,9 @@ the working tree and from <parent-rev> and compares them kernel by kernel.
 
 Both trees are compiled with _build.FLAGS minus -shared / -fPIC, plus --cuda-device-only -S; <parent-rev>'s csrc/ and
 include/ are checked out into a temporary directory.  Lines that name the per-unit `__hip_cuid_<hash>` symbol are dropped
-(the hash follows the source text).  Per unit the script prints `identical`, or the mangled names of the kernels whose
-text differs.  Nothing else about the assembly is printed.  Exit status 1 unless every unit is identical.
+(the hash follows the source text), and the ordinal of a function inside its unit is taken out of its local labels, so a
+new template instantiation does not show up as a change of every kernel behind it.  Per unit the script prints
+`identical`, or the mangled names of the kernels whose text differs (new ones: `only in the tree`).  Nothing else about the assembly is printed.  Exit status 1 unless every unit is identical.
 
 Usage: python scripts/device_asm_diff.py <parent-rev> [--jobs N]   (N <= 16, default 8; needs hipcc, no GPU)"""
 import argparse
@@ -40,6 +41,11 @@ def functions(path):
         for ln in f:
             if "__hip_cuid_" in ln:
                 continue
+            # local labels carry the function's ordinal in its unit (.LBB<k>_<n>, .Lfunc_begin<k>, .Lfunc_end<k>, .LJTI<k>_<n>,
+            # and BB<k>_<n> in the loop comments): a new template instantiation ahead of a kernel renumbers them without touching
+            # an instruction (and moves the column of the comment behind a label by a digit)
+            ln = re.sub(r"\.(LBB|LJTI|Lfunc_begin|Lfunc_end)\d+", r".\1#", ln)
+            ln = re.sub(r"\s+;", " ;", re.sub(r"\bBB\d+_", "BB#_", ln))
             m = re.match(r"\s*\.type\s+([^,\s]+),@function", ln) or re.match(r"\s*\.amdhsa_kernel\s+(\S+)", ln)
             if m:
                 if cur is not None:  # (a kernel's descriptor follows its code, before .Lfunc_end)
