@@ -170,7 +170,8 @@ int mppi_build_lane_map(mppi_handle_t h, int slot, int nx, int ny, float cell_si
 /* Read a slot's grid back (cells_host may be NULL to query nx, ny only).  Synchronises the device. */
 int mppi_download_map(mppi_handle_t h, int slot, uint8_t* cells_host, int* nx, int* ny);
 /* racing_controller.reference_path = calc_ref_trajectory(...) (example/racing.py:73-81):
- * ref [rows][4] = (x, y, yaw, v_target), rows >= T (the cost reads rows 0..T-1). */
+ * ref [rows][4] = (x, y, yaw, v_target), rows >= T (the cost reads rows 0..T-1).  MPPI_E_INVALID on a handle of a model
+ * without a reference window (every model but the two racing ones). */
 int mppi_set_reference(mppi_handle_t h, const float* ref_host, int rows, void* stream);
 /* Learned dynamics for MPPI_MODEL_MLP41 / MPPI_MODEL_MLP42: the weights of a multi-layer perceptron with 4 states,
  * dc = 1 / 2 controls, `hidden_layers` = 1 or 2 hidden layers of MPPI_MLP_HIDDEN = 32 units and 4 outputs, as ONE table of
@@ -211,7 +212,7 @@ int mppi_set_mlp(mppi_handle_t h, const float* table_host, int n_floats, int hid
  * host wait: a host table (on_device = 0) is checked (finite, w >= 0), staged and copied like mppi_set_reference's window;
  * a device table (on_device != 0) is padded by one small kernel, so an obstacle predictor on the device never meets the
  * host — and is NOT checked (that would need a host wait): the predictor keeps its values finite and w >= 0.  A horizon whose
- * T rows (128 B each) do not fit in a block's LDS is refused at solve time (MPPI_E_INVALID).  The buffer grows (blocking, set-up path) only when `rows` exceeds every earlier call's.  The table may be replaced
+ * T rows (128 B each) do not fit in a block's LDS is refused at solve time (MPPI_E_INVALID).  The buffer (the handle's one step table, at least T + 1 rows from the first call on) grows, blocking on the set-up path, only when `rows` exceeds what it holds, and keeps the rows it held.  The table may be replaced
  * before every solve; re-rolls of an earlier solve (get_top_samples, a lazily completed state sequence) need the dynamics
  * only and are not affected.  MPPI_E_INVALID for another model's handle, n outside 0..8, rows < 1; solves without a table
  * or with fewer rows than the horizon return MPPI_E_STATE.  mppi_clone_state copies the table.

@@ -332,21 +332,16 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
     }
     dm.ctx.ref = nullptr; dm.ctx.ref_rows = 0;
     dm.ref_part_rows = dm.disc_part_rows = 0;
-    if (sm.ref) {  // (racing with discs: the one step table carries both parts; the count rides in ctx.P, copied above)
-        if (int rc = reserve_ref(dst, (int)(sm.ref.n / (size_t)ref_stride(src->cfg.model)))) return rc;
+    if (sm.ref) {  // the step table with the rows of each part (the disc count was copied with ctx)
+        if (int rc = reserve_step_table(dst, (int)(sm.ref.n / (size_t)step_layout(src->cfg.model).stride))) return rc;
         if (int rc = clone_buf(dst, dm.ref.p, sm.ref.p, sm.ref.n)) return rc;
         dm.ref_part_rows = sm.ref_part_rows; dm.disc_part_rows = sm.disc_part_rows;
-        if (sm.ctx.ref) { dm.ctx.ref = dm.ref; dm.ctx.ref_rows = sm.ctx.ref_rows; }
+        publish_step_table(dst);
     }
     if (sm.mlp && sm.ctx.ref) {  // learned dynamics: the weight table, with the flags that ride in ref_rows
         if (dm.mlp.n != sm.mlp.n) HIP_TRY(dst, dm.mlp.alloc(sm.mlp.n));
         CLONE(model.mlp);
         dm.ctx.ref = dm.mlp; dm.ctx.ref_rows = sm.ctx.ref_rows;
-    }
-    if (sm.discs && sm.ctx.ref) {  // moving discs: the padded table; rows ride in ref_rows, the count in tan_small (copied with ctx)
-        if (dm.discs.n != sm.discs.n) HIP_TRY(dst, dm.discs.alloc(sm.discs.n));
-        CLONE(model.discs);
-        dm.ctx.ref = dm.discs; dm.ctx.ref_rows = sm.ctx.ref_rows;
     }
     if (sm.center_n) {
         HIP_TRY(dst, dm.center8.alloc(sm.center8.n));

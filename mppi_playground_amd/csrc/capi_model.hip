@@ -58,44 +58,45 @@ static int upload_ints(mppi_handle_t h, const int32_t* src, size_t count, DevBuf
     return MPPI_OK;
 }
 
-// make sure h->model.ref holds `rows` rows of the model's stride (blocking reallocation: set-up path).  Racing with discs:
-// the table has a second writer, so a larger buffer starts from the old one's rows (the stride is the same: they keep
-// their places) and from at least the horizon, so that the racing tick's T + 1 window rows do not move a T-row disc part.
-int reserve_ref(mppi_handle_t h, int rows) {
-    const size_t stride = (size_t)ref_stride(h->cfg.model);
-    if ((size_t)rows * stride <= h->model.ref.n) return MPPI_OK;
-    if (h->model.ref) HIP_TRY(h, hipDeviceSynchronize());
-    if (h->cfg.model != MPPI_MODEL_RACING_DISCS) {
-        HIP_TRY(h, h->model.ref.alloc(stride * (size_t)rows));
-        return MPPI_OK;
-    }
+// Make sure the step table holds `rows` rows (blocking reallocation: set-up path).  The table may have two writers, so a
+// larger buffer starts from the old one's rows (the stride is the same: they keep their places) and from at least T + 1
+// rows, so that the racing tick's window rows do not move a T-row disc part.
+int reserve_step_table(mppi_handle_t h, int rows) {
+    auto& m = h->model;
+    const size_t stride = (size_t)step_layout(h->cfg.model).stride;
+    if ((size_t)rows * stride <= m.ref.n) return MPPI_OK;
+    if (m.ref) HIP_TRY(h, hipDeviceSynchronize());
     DevBuf<float> grown;
     const size_t floats = stride * (size_t)std::max(rows, h->d.T + 1);
     HIP_TRY(h, grown.alloc(floats));
     HIP_TRY(h, hipMemset(grown, 0, sizeof(float) * floats));
-    if (h->model.ref) HIP_TRY(h, hipMemcpy(grown, h->model.ref, sizeof(float) * h->model.ref.n, hipMemcpyDeviceToDevice));
-    h->model.ref = std::move(grown);  // (swaps: the old buffer is freed with `grown`)
-    if (h->model.ctx.ref) h->model.ctx.ref = h->model.ref;
+    if (m.ref) HIP_TRY(h, hipMemcpy(grown, m.ref, sizeof(float) * m.ref.n, hipMemcpyDeviceToDevice));
+    m.ref = std::move(grown);  // (swaps: the old buffer is freed with `grown`)
+    if (m.ctx.ref) m.ctx.ref = m.ref;
     return MPPI_OK;
 }
 
-// Racing with discs: aim ctx.ref at the step table once BOTH of its parts have been written (check_ready names what is
-// missing until then); ref_rows = the rows both parts cover.
-static void publish_step_table(mppi_handle_t h) {
+// Aim ctx.ref at the step table once every part its layout has has been written (check_ready names what is missing
+// until then); ref_rows = the rows all of them cover.
+void publish_step_table(mppi_handle_t h) {
     auto& m = h->model;
-    const int rows = std::min(m.ref_part_rows, m.disc_part_rows);
+    const StepLayout L = step_layout(h->cfg.model);
+    const int rows = !L.has_discs() ? m.ref_part_rows : !L.has_ref() ? m.disc_part_rows : std::min(m.ref_part_rows, m.disc_part_rows);
     m.ctx.ref = rows > 0 ? m.ref.p : nullptr;
     m.ctx.ref_rows = rows;
 }
-// the reference part of the model's table has `rows` rows now
+// the reference part of the table has `rows` rows now
 static void reference_written(mppi_handle_t h, int rows) {
-    if (h->cfg.model == MPPI_MODEL_RACING_DISCS) {
-        h->model.ref_part_rows = rows;
-        publish_step_table(h);
-        return;
-    }
-    h->model.ctx.ref = h->model.ref;
-    h->model.ctx.ref_rows = rows;
+    h->model.ref_part_rows = rows;
+    publish_step_table(h);
+}
+
+// `rows` rows of `width` floats from rows `spitch` floats apart to rows `dpitch` floats apart: between a contiguous block
+// and one part of the step table, in either direction.  One plain copy where both sides are contiguous.
+static hipError_t copy_rows(float* dst, size_t dpitch, const float* src, size_t spitch, size_t width, int rows, hipMemcpyKind kind,
+                            hipStream_t s) {
+    if (dpitch == width && spitch == width) return hipMemcpyAsync(dst, src, sizeof(float) * width * (size_t)rows, kind, s);
+    return hipMemcpy2DAsync(dst, sizeof(float) * dpitch, src, sizeof(float) * spitch, sizeof(float) * width, (size_t)rows, kind, s);
 }
 
 // value `f` of the padded table [rows][8][4] from the caller's [rows][n][4]: slots past n hold {0, 0, r2 = -1, w = 0}
@@ -106,26 +107,12 @@ __host__ __device__ inline float disc_padded(const float* discs, int n, size_t f
     return c == 2 ? DISC_PAD_R2 : c == 3 ? DISC_PAD_W : 0.0f;
 }
 
-// mppi_set_discs from a device table: the padding, in stream order (one thread per value of the padded table)
-__global__ __launch_bounds__(BLOCK) void disc_rows_kernel(const float* __restrict__ discs, int rows, int n, float* __restrict__ out) {
-    const size_t f = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (f < (size_t)rows * DISC_ROW) out[f] = disc_padded(discs, n, f);
-}
-// the same into the disc part of a wider step row (racing with discs: `stride` floats per row, the discs from float `off`);
-// the other floats of the row are not touched
+// mppi_set_discs from a device table: the padding, in stream order (one thread per value of the padded rows), into the
+// disc part of the step rows (`stride` floats per row, the discs from float `off`); the other floats of a row are not touched
 __global__ __launch_bounds__(BLOCK) void disc_rows_strided_kernel(const float* __restrict__ discs, int rows, int n,
                                                                   float* __restrict__ out, int stride, int off) {
     const size_t f = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (f < (size_t)rows * DISC_ROW) out[(f / DISC_ROW) * (size_t)stride + off + f % DISC_ROW] = disc_padded(discs, n, f);
-}
-
-// make sure h->model.discs holds `rows` rows (blocking reallocation: set-up path; at least the horizon from the start)
-static int reserve_discs(mppi_handle_t h, int rows) {
-    if ((size_t)rows * DISC_ROW <= h->model.discs.n) return MPPI_OK;
-    if (h->model.discs) HIP_TRY(h, hipDeviceSynchronize());
-    h->model.ctx.ref = nullptr; h->model.ctx.ref_rows = 0;
-    HIP_TRY(h, h->model.discs.alloc((size_t)DISC_ROW * (size_t)std::max(rows, h->d.T)));
-    return MPPI_OK;
 }
 
 }  // namespace mppi
@@ -238,9 +225,11 @@ int mppi_download_map(mppi_handle_t h, int slot, uint8_t* cells_host, int* nx, i
 int mppi_set_reference(mppi_handle_t h, const float* ref, int rows, void* stream) {
     if (!h || !ref || rows < 1) return fail(h, MPPI_E_INVALID, "bad reference");
     if (is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "a learned-dynamics handle has no reference window");
-    if (h->cfg.model == MPPI_MODEL_NAV2D_DISCS) return fail(h, MPPI_E_INVALID, "a moving-disc handle has no reference window");
+    const StepLayout L = step_layout(h->cfg.model);
+    if (!L.has_ref())
+        return fail(h, MPPI_E_INVALID, L.has_discs() ? "a moving-disc handle has no reference window" : "the reference window belongs to the racing models");
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = reserve_ref(h, rows)) return rc;
+    if (int rc = reserve_step_table(h, rows)) return rc;
     float* st = nullptr; hipEvent_t ev = nullptr;
     if (int rc = stage_slot(h, (size_t)rows * 8, &st, &ev)) return rc;
     for (int i = 0; i < rows; ++i) {
@@ -249,11 +238,7 @@ int mppi_set_reference(mppi_handle_t h, const float* ref, int rows, void* stream
         o[4] = sinf(o[2]); o[5] = cosf(o[2]);  // torch.sin/cos of the fp32 scalar, racing.py:127-139
         o[6] = o[7] = 0.0f;
     }
-    const size_t pitch = sizeof(float) * (size_t)ref_stride(h->cfg.model);
-    if (pitch == sizeof(float) * 8)
-        HIP_TRY(h, hipMemcpyAsync(h->model.ref, st, sizeof(float) * 8 * (size_t)rows, hipMemcpyHostToDevice, s));
-    else  // racing with discs: floats 0-7 of every step row, the discs behind them stay
-        HIP_TRY(h, hipMemcpy2DAsync(h->model.ref, pitch, st, sizeof(float) * 8, sizeof(float) * 8, (size_t)rows, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, copy_rows(h->model.ref, L.stride, st, L.ref_floats, L.ref_floats, rows, hipMemcpyHostToDevice, s));  // (discs behind the row stay)
     HIP_TRY(h, hipEventRecord(ev, s));
     reference_written(h, rows);
     return MPPI_OK;
@@ -294,66 +279,37 @@ int mppi_set_discs(mppi_handle_t h, const float* discs, int rows, int n, int on_
             if (!std::isfinite(discs[i]) || (i % DISC_FLOATS == 3 && discs[i] < 0.0f))
                 return fail(h, MPPI_E_INVALID, "disc table: every value must be finite and every penalty >= 0");
     hipStream_t s = (hipStream_t)stream;
-    if (h->cfg.model == MPPI_MODEL_RACING_DISCS) {  // the disc part (floats 8-39) of the step table the reference window shares
-        if (int rc = reserve_ref(h, rows)) return rc;
-        const int stride = ref_stride(h->cfg.model), off = disc_offset(h->cfg.model);
-        if (on_device) {
-            hipLaunchKernelGGL(disc_rows_strided_kernel, dim3((unsigned)((floats + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, discs,
-                               rows, n, h->model.ref.p, stride, off);
-            HIP_TRY(h, hipGetLastError());
-        } else {
-            float* st = nullptr; hipEvent_t ev = nullptr;
-            if (int rc = stage_slot(h, floats, &st, &ev)) return rc;
-            for (size_t f = 0; f < floats; ++f) st[f] = disc_padded(discs, n, f);
-            HIP_TRY(h, hipMemcpy2DAsync(h->model.ref.p + off, sizeof(float) * stride, st, sizeof(float) * DISC_ROW,
-                                        sizeof(float) * DISC_ROW, (size_t)rows, hipMemcpyHostToDevice, s));
-            HIP_TRY(h, hipEventRecord(ev, s));
-        }
-        h->model.disc_part_rows = rows;
-        set_disc_count(h->model.ctx, h->cfg.model, n);
-        publish_step_table(h);
-        return MPPI_OK;
-    }
-    if (int rc = reserve_discs(h, rows)) return rc;
+    const StepLayout L = step_layout(h->cfg.model);
+    if (int rc = reserve_step_table(h, rows)) return rc;
     if (on_device) {
-        hipLaunchKernelGGL(disc_rows_kernel, dim3((unsigned)((floats + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, discs, rows, n,
-                           h->model.discs.p);
+        hipLaunchKernelGGL(disc_rows_strided_kernel, dim3((unsigned)((floats + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, discs, rows, n,
+                           h->model.ref.p, L.stride, L.disc_off);
         HIP_TRY(h, hipGetLastError());
     } else {
         float* st = nullptr; hipEvent_t ev = nullptr;
         if (int rc = stage_slot(h, floats, &st, &ev)) return rc;
         for (size_t f = 0; f < floats; ++f) st[f] = disc_padded(discs, n, f);
-        HIP_TRY(h, hipMemcpyAsync(h->model.discs, st, sizeof(float) * floats, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, copy_rows(h->model.ref.p + L.disc_off, L.stride, st, DISC_ROW, DISC_ROW, rows, hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipEventRecord(ev, s));
     }
-    h->model.ctx.ref = h->model.discs;
-    h->model.ctx.ref_rows = rows;
+    h->model.disc_part_rows = rows;
     set_disc_count(h->model.ctx, h->cfg.model, n);  // (disc_count: mppi_models.hpp)
+    publish_step_table(h);
     return MPPI_OK;
 }
 
 int mppi_get_discs(mppi_handle_t h, float* out, int* rows_out, int* n_out, int on_device, void* stream) {
     if (!h) return MPPI_E_INVALID;
     if (!has_discs(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the disc table belongs to the moving-disc models");
-    hipStream_t s = (hipStream_t)stream;
-    if (h->cfg.model == MPPI_MODEL_RACING_DISCS) {
-        const int rows = h->model.disc_part_rows;
-        if (rows < 1) return fail(h, MPPI_E_STATE, "no disc table: call mppi_set_discs first");
-        if (rows_out) *rows_out = rows;
-        if (n_out) *n_out = disc_count(h->model.ctx, h->cfg.model);
-        if (!out) return MPPI_OK;
-        HIP_TRY(h, hipMemcpy2DAsync(out, sizeof(float) * DISC_ROW, h->model.ref.p + disc_offset(h->cfg.model),
-                                    sizeof(float) * ref_stride(h->cfg.model), sizeof(float) * DISC_ROW, (size_t)rows,
-                                    on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        if (!on_device) HIP_TRY(h, hipStreamSynchronize(s));
-        return MPPI_OK;
-    }
-    if (!h->model.ctx.ref) return fail(h, MPPI_E_STATE, "no disc table: call mppi_set_discs first");
-    if (rows_out) *rows_out = h->model.ctx.ref_rows;
-    if (n_out) *n_out = disc_count(h->model.ctx);
+    const StepLayout L = step_layout(h->cfg.model);
+    const int rows = h->model.disc_part_rows;  // (the discs may be there before the window is)
+    if (rows < 1) return fail(h, MPPI_E_STATE, "no disc table: call mppi_set_discs first");
+    if (rows_out) *rows_out = rows;
+    if (n_out) *n_out = disc_count(h->model.ctx, h->cfg.model);
     if (!out) return MPPI_OK;
-    HIP_TRY(h, hipMemcpyAsync(out, h->model.discs, sizeof(float) * DISC_ROW * (size_t)h->model.ctx.ref_rows,
-                              on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, copy_rows(out, DISC_ROW, h->model.ref.p + L.disc_off, L.stride, DISC_ROW, rows,
+                         on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     if (!on_device) HIP_TRY(h, hipStreamSynchronize(s));
     return MPPI_OK;
 }
@@ -378,7 +334,7 @@ int mppi_set_center_path(mppi_handle_t h, const float* path_host, int n, const i
     HIP_TRY(h, h->model.win_dind.alloc((size_t)rows));
     HIP_TRY(h, hipMemcpy(h->model.win_dind, dind_host, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice));
     if (!h->model.path_index) HIP_TRY(h, h->model.path_index.alloc_set(1, 0));
-    if (int rc = reserve_ref(h, rows)) return rc;
+    if (int rc = reserve_step_table(h, rows)) return rc;
     h->model.center_n = n; h->model.win_rows = rows; h->model.win_v = v_target;
     return MPPI_OK;
 }
@@ -387,7 +343,7 @@ int mppi_ref_window(mppi_handle_t h, const float* state_dev, void* stream) {
     if (!h) return MPPI_E_INVALID;
     if (!h->model.center_n) return fail(h, MPPI_E_STATE, "mppi_ref_window before mppi_set_center_path");
     const RefWindowCtx w{h->model.center8, h->model.win_dind, h->model.path_index, h->model.center_n, h->model.win_rows, h->model.win_v,
-                         ref_stride(h->cfg.model)};
+                         step_layout(h->cfg.model).stride};
     hipLaunchKernelGGL(ref_window_kernel, dim3(1), dim3(REFWIN_BLOCK), 0, (hipStream_t)stream, w,
                        state_dev ? state_dev : h->core.x0_cur, h->model.ref);
     HIP_TRY(h, hipGetLastError());
@@ -414,13 +370,12 @@ int mppi_get_path_index(mppi_handle_t h, int32_t* cind_out_host, void* stream) {
 int mppi_get_reference(mppi_handle_t h, float* ref_out, int rows, int on_device, void* stream) {
     if (!h || !ref_out || rows < 1) return fail(h, MPPI_E_INVALID, "bad get_reference arguments");
     if (is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "a learned-dynamics handle has no reference window");
-    if (h->cfg.model == MPPI_MODEL_NAV2D_DISCS) return fail(h, MPPI_E_INVALID, "a moving-disc handle has no reference window");
-    const bool two_parts = h->cfg.model == MPPI_MODEL_RACING_DISCS;  // (the window may be there before the discs are)
-    if (two_parts ? rows > h->model.ref_part_rows : (!h->model.ctx.ref || rows > h->model.ctx.ref_rows))
+    const StepLayout L = step_layout(h->cfg.model);
+    if (L.has_discs() && !L.has_ref()) return fail(h, MPPI_E_INVALID, "a moving-disc handle has no reference window");
+    if (rows > h->model.ref_part_rows)  // (the window may be there before the discs are)
         return fail(h, MPPI_E_STATE, "no reference window of that many rows");
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipMemcpy2DAsync(ref_out, 4 * sizeof(float), h->model.ref, sizeof(float) * ref_stride(h->cfg.model), 4 * sizeof(float), (size_t)rows,
-                                on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, copy_rows(ref_out, 4, h->model.ref, L.stride, 4, rows, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     if (!on_device) HIP_TRY(h, hipStreamSynchronize(s));
     return MPPI_OK;
 }

@@ -290,10 +290,12 @@ struct MppiSolver {
         bool params_set = false;
         DevBuf<uint8_t> map_cells[2];
         DevBuf<uint8_t> map_pad;       // padded (and, for racing, summed) grid of the FAST lookup
-        DevBuf<float> ref;             // [rows][8] reference window; racing with discs: the step table [rows][40] (ref_stride)
-        int ref_part_rows = 0;         // racing with discs: rows of the table whose reference part (floats 0-7) is written ...
-        int disc_part_rows = 0;        // ... and whose disc part (floats 8-39) is; ctx.ref is set once both are (publish_step_table)
-        DevBuf<float> discs;           // [rows][8][4] padded disc table of the moving-disc model (mppi_set_discs); ctx.ref points at it
+        // the step table [rows][step_layout(model).stride] (mppi_models.hpp) and the rows each of its parts has been written
+        // for; a part the layout does not have stays 0 and counts as complete.  publish_step_table aims ctx.ref at the table
+        // once every part is there.
+        DevBuf<float> ref;
+        int ref_part_rows = 0;         // reference part: mppi_set_reference / mppi_ref_window
+        int disc_part_rows = 0;        // disc part: mppi_set_discs
         DevBuf<float> mlp;             // weight table of the learned-dynamics models (mppi_set_mlp); ctx.ref points at it
         // device-resident reference window (mppi_set_center_path / mppi_ref_window)
         DevBuf<float> center8;         // [n][8] centre line with sin/cos of the yaw
@@ -377,8 +379,6 @@ inline bool model_dims(int model, ModelDims& md) {
 }
 // nav2d and its moving-disc variant: one set of dynamics, parameters, maps and host-checked preconditions
 inline bool is_nav2d(int model) { return model == MPPI_MODEL_NAV2D || model == MPPI_MODEL_NAV2D_DISCS; }
-// the models that carry a disc table (mppi_set_discs)
-inline bool has_discs(int model) { return model == MPPI_MODEL_NAV2D_DISCS || model == MPPI_MODEL_RACING_DISCS; }
 // parameters the dynamics of `model` read (the models without any take none)
 inline int model_param_count(int model) {
     return is_racing_model(model) ? MPPI_RP_COUNT : is_nav2d(model) ? MPPI_NP_COUNT
@@ -511,25 +511,17 @@ inline int check_ready(mppi_handle_t h) {
     if ((is_nav2d(m) || is_racing_model(m)) && !h->model.map_cells[0])
         return fail(h, MPPI_E_STATE, "obstacle map (slot 0) not uploaded");
     if (is_racing_model(m) && !h->model.map_cells[1]) return fail(h, MPPI_E_STATE, "lane map (slot 1) not uploaded");
-    if (m == MPPI_MODEL_RACING && (!h->model.ctx.ref || h->model.ctx.ref_rows < h->d.T))
-        return fail(h, MPPI_E_STATE, "reference path not set or shorter than the horizon");
-    // racing with discs: one step table, two writers (capi_model.hip); ctx.ref is aimed at it once BOTH parts are there
-    if (m == MPPI_MODEL_RACING_DISCS && h->model.ref_part_rows < h->d.T)
-        return fail(h, MPPI_E_STATE, "reference path not set or shorter than the horizon");
-    if (m == MPPI_MODEL_RACING_DISCS && h->model.disc_part_rows < 1)
-        return fail(h, MPPI_E_STATE, "no disc table: call mppi_set_discs first");
-    if (m == MPPI_MODEL_RACING_DISCS && h->model.disc_part_rows < h->d.T)
-        return fail(h, MPPI_E_STATE, "disc table has fewer rows than the horizon");
-    if (m == MPPI_MODEL_RACING_DISCS && (!h->model.ctx.ref || h->model.ctx.ref_rows < h->d.T))
-        return fail(h, MPPI_E_STATE, "step table of the racing-with-discs model is incomplete");
     if (is_mlp(m) && !h->model.ctx.ref) return fail(h, MPPI_E_STATE, "no weight table: call mppi_set_mlp first");
-    if (m == MPPI_MODEL_NAV2D_DISCS && !h->model.ctx.ref) return fail(h, MPPI_E_STATE, "no disc table: call mppi_set_discs first");
-    if (m == MPPI_MODEL_NAV2D_DISCS && h->model.ctx.ref_rows < h->d.T)
+    // the step table (mppi_models.hpp): every part its layout has covers the horizon (ctx.ref is aimed at it once they do)
+    const StepLayout L = step_layout(m);
+    if (L.has_ref() && h->model.ref_part_rows < h->d.T)
+        return fail(h, MPPI_E_STATE, "reference path not set or shorter than the horizon");
+    if (L.has_discs() && h->model.disc_part_rows < 1) return fail(h, MPPI_E_STATE, "no disc table: call mppi_set_discs first");
+    if (L.has_discs() && h->model.disc_part_rows < h->d.T)
         return fail(h, MPPI_E_STATE, "disc table has fewer rows than the horizon");
     // the rollout kernels keep T rows of the table in LDS (mppi_lds.hpp): refuse a horizon whose rows do not fit next to the
     // mean groups here, by name, instead of as a failed launch
-    if (has_discs(m) &&
-        sizeof(float) * RolloutLds::floats(h->d.R, h->d.T, h->d.row, disc_offset(m) + DISC_ROW, true) > (size_t)h->lds_max)
+    if (L.has_discs() && sizeof(float) * RolloutLds::floats(h->d.R, h->d.T, h->d.row, L.stride, true) > (size_t)h->lds_max)
         return fail(h, MPPI_E_INVALID, "horizon too long for the moving-disc model: its table rows do not fit in LDS");
     return MPPI_OK;
 }
@@ -569,7 +561,8 @@ int stage_slot(mppi_handle_t h, size_t floats, float** out, hipEvent_t* ev);
 // capi_model.hip
 void refresh_pad(mppi_handle_t h, hipStream_t s);
 int prepare_map(mppi_handle_t h, int slot, int nx, int ny, float cell, float ox, float oy);
-int reserve_ref(mppi_handle_t h, int rows);
+int reserve_step_table(mppi_handle_t h, int rows);
+void publish_step_table(mppi_handle_t h);
 
 // the per-column sigma table the sampler reads (see MppiSolver::Cov)
 inline float* sigma_table(mppi_handle_t h) { return h->wide ? h->core.coltab.p : h->cov.sigtab.p; }

@@ -64,24 +64,43 @@ constexpr int mlp_table_floats(int dc) {
     return MPPI_MLP_HIDDEN * (4 + dc) + MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN * MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN + 4 * MPPI_MLP_HIDDEN + 4;
 }
 
-// The moving-disc model (MPPI_MODEL_NAV2D_DISCS; mppi_set_discs): the padded table [rows][8][4] is ModelCtx::ref and
-// ref_rows its row count (the solve checks it against the horizon); the launch-uniform number of discs per row rides in
-// ModelCtx::tan_small, a racing flag this model has no other use for, so the kernels' argument struct is what it was.
+// The step table: the models whose cost reads step-constant values carry ONE table with one row per horizon step.  It is
+// ModelCtx::ref, ref_rows is the number of rows every part of it covers (the solve checks it against the horizon), and the
+// rollout kernels stage T rows of it into LDS.  A row has up to two parts, each with a writer of its own on the host:
+//   the reference part   racing's reference row in floats [0, ref_floats)         (mppi_set_reference / mppi_ref_window)
+//   the disc part        MPPI_MAX_DISCS padded discs {cx, cy, r2, w} in floats [disc_off, disc_off + DISC_ROW), each disc
+//                        16-byte aligned                                           (mppi_set_discs)
+// step_layout(model) says which floats of a row belong to whom; the functors' KROW is its stride (asserted at the end of
+// this file).  The launch-uniform number of discs per row rides where the model has a free field, so that the kernels'
+// argument struct is what it was: nav2d with discs in ModelCtx::tan_small (a racing flag), racing with discs in the first
+// P[] slot behind racing's parameters, as the BITS of the integer (no conversion on the device; mppi_set_model_params
+// writes MPPI_RP_COUNT values and leaves it alone).
 static_assert(DISC_ROW == 4 * MPPI_MAX_DISCS, "mppi_discs.hpp spells the row of MPPI_MAX_DISCS discs");
-// Racing with moving discs (MPPI_MODEL_RACING_DISCS): racing reads both `ref` and `tan_small` itself.  The table is still
-// ModelCtx::ref — ONE table of RACING_DISCS_KROW floats per step, the reference row in floats 0-7 and the eight padded discs
-// behind it (each disc 16-byte aligned) — and the count waits in the first P[] slot behind racing's parameters, as the BITS
-// of the integer (no conversion on the device; mppi_set_model_params writes MPPI_RP_COUNT values and leaves it alone).
 constexpr int RACING_REF_ROW = 8;                            // floats of a racing reference row
 constexpr int RACING_DISCS_KROW = RACING_REF_ROW + DISC_ROW;  // 40
 constexpr int RACING_DISCS_SLOT = MPPI_RP_COUNT;              // P[] slot of the disc count
 static_assert(RACING_DISCS_SLOT < MPPI_MAX_PARAMS, "the disc count needs a free parameter slot");
-static_assert(RACING_REF_ROW % 4 == 0 && RACING_DISCS_KROW % 4 == 0, "discs stay 16-byte aligned behind the reference row");
 constexpr bool is_racing_model(int model) { return model == MPPI_MODEL_RACING || model == MPPI_MODEL_RACING_DISCS; }
-// floats per step of the table ModelCtx::ref points at, for the models whose reference window the host entry points write
-constexpr int ref_stride(int model) { return model == MPPI_MODEL_RACING_DISCS ? RACING_DISCS_KROW : RACING_REF_ROW; }
-// first float of the discs inside a step row
-constexpr int disc_offset(int model) { return model == MPPI_MODEL_RACING_DISCS ? RACING_REF_ROW : 0; }
+struct StepLayout {
+    int stride;      // floats per step row (0: the model has no step table)
+    int ref_floats;  // the reference part is floats [0, ref_floats) (0: none)
+    int disc_off;    // the disc part starts at this float (-1: none)
+    constexpr bool has_ref() const { return ref_floats > 0; }
+    constexpr bool has_discs() const { return disc_off >= 0; }
+};
+constexpr StepLayout step_layout(int model) {
+    return model == MPPI_MODEL_RACING         ? StepLayout{RACING_REF_ROW, RACING_REF_ROW, -1}
+           : model == MPPI_MODEL_NAV2D_DISCS  ? StepLayout{DISC_ROW, 0, 0}
+           : model == MPPI_MODEL_RACING_DISCS ? StepLayout{RACING_DISCS_KROW, RACING_REF_ROW, RACING_REF_ROW}
+                                              : StepLayout{0, 0, -1};
+}
+static_assert(step_layout(MPPI_MODEL_RACING_DISCS).disc_off % 4 == 0 && step_layout(MPPI_MODEL_RACING_DISCS).stride % 4 == 0,
+              "discs stay 16-byte aligned behind the reference row");
+// the models that carry a disc table (mppi_set_discs)
+constexpr bool has_discs(int model) { return step_layout(model).has_discs(); }
+// the descriptor's two fields under the names the host programs of the tests read them by
+constexpr int ref_stride(int model) { return step_layout(model).stride; }
+constexpr int disc_offset(int model) { return step_layout(model).disc_off; }
 // The number of discs per row: the one accessor both disc models go through (`model`: a constant where a kernel calls it)
 MPPI_HD int disc_count(const ModelCtx& c, int model = MPPI_MODEL_NAV2D_DISCS) {
     if (model != MPPI_MODEL_RACING_DISCS) return c.tan_small;
@@ -211,4 +230,13 @@ template <class M, class = void>
 struct EntryGeneral { static constexpr bool value = false; };
 template <class M>
 struct EntryGeneral<M, decltype((void)M::ENTRY_GENERAL)> { static constexpr bool value = M::ENTRY_GENERAL; };
+
+// every functor stages the row its model's step layout describes
+template <int MODEL>
+constexpr bool krow_is_stride() { return ModelT<MODEL, 0>::KROW == step_layout(MODEL).stride; }
+static_assert(krow_is_stride<MPPI_MODEL_PENDULUM>() && krow_is_stride<MPPI_MODEL_CARTPOLE>() && krow_is_stride<MPPI_MODEL_MOUNTAINCAR>() &&
+              krow_is_stride<MPPI_MODEL_NAV2D>() && krow_is_stride<MPPI_MODEL_RACING>() && krow_is_stride<MPPI_MODEL_MJCARTPOLE>() &&
+              krow_is_stride<MPPI_MODEL_GOALZONE>() && krow_is_stride<MPPI_MODEL_MLP41>() && krow_is_stride<MPPI_MODEL_MLP42>() &&
+              krow_is_stride<MPPI_MODEL_NAV2D_DISCS>() && krow_is_stride<MPPI_MODEL_RACING_DISCS>(),
+              "a functor's KROW is the stride of step_layout(model)");
 }  // namespace mppi

@@ -20,10 +20,9 @@ from typing import Tuple
 
 import torch
 
+from envs.discs import MAX_DISCS, disc_hits, disc_penalty
 from envs.navigation_2d import Navigation2DEnv, _nav_inputs
 from pi_mpc.native import native_model
-
-MAX_DISCS = 8  # MPPI_MAX_DISCS
 
 
 def _moving_inputs(env: "MovingObstacleNav2DEnv") -> dict:
@@ -99,21 +98,9 @@ class MovingObstacleNav2DEnv(Navigation2DEnv):
         goal_cost = torch.sqrt((gx * gx + gy * gy).double()).to(state.dtype)
         occ = self._obstacle_map.compute_cost(state[:, :2].unsqueeze(1)).squeeze(1)
         base = goal_cost + self.obstacle_weight * occ
-        row = self._disc_table[info["t"]]  # [K, 4]: the discs where they are predicted to be at this step
-        pen = torch.zeros_like(x)
-        for j in range(row.shape[0]):  # in slot order, like the device
-            dx, dy = x - row[j, 0], y - row[j, 1]
-            d2 = dx * dx + dy * dy
-            pen = pen + torch.where(d2 <= row[j, 2], row[j, 3], torch.zeros_like(x))
-        return base + pen
+        return base + disc_penalty(self._disc_table[info["t"]], x, y)  # the discs where they are predicted to be at this step
 
     def collision_check(self, state: torch.Tensor) -> torch.Tensor:
         """The parent's static-map test plus the discs where they are NOW (row 0); > 0 means in collision."""
         hit = super().collision_check(state)
-        row = self._disc_table[0]
-        xy = state[:, :, :2]
-        for j in range(row.shape[0]):
-            d = xy - row[j, 0:2]
-            inside = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) <= row[j, 2]
-            hit = hit + inside.to(hit.dtype).reshape(hit.shape)
-        return hit
+        return hit + disc_hits(self._disc_table[0], state).to(hit.dtype).reshape(hit.shape)

@@ -20,11 +20,10 @@ from typing import Tuple
 
 import torch
 
+from envs.discs import MAX_DISCS, disc_hits, disc_penalty
 from envs.racing_controller import _racing_cost_inputs, racing_controller
 from envs.racing_env import RacingEnv, _racing_dyn_inputs
 from pi_mpc.native import native_model
-
-MAX_DISCS = 8  # MPPI_MAX_DISCS
 
 
 class OpponentRacingEnv(RacingEnv):
@@ -100,12 +99,7 @@ class OpponentRacingEnv(RacingEnv):
 
     def opponent_hits(self, state: torch.Tensor) -> torch.Tensor:
         """How many cars, where they are NOW (row 0), each position of state [..., >= 2] lies in."""
-        row = self._opp_table[0]
-        hit = torch.zeros(state.shape[:-1], device=state.device, dtype=state.dtype)
-        for j in range(row.shape[0]):
-            dx, dy = state[..., 0] - row[j, 0], state[..., 1] - row[j, 1]
-            hit = hit + ((dx * dx + dy * dy) <= row[j, 2]).to(hit.dtype)
-        return hit
+        return disc_hits(self._opp_table[0], state)
 
     def collision_check(self, state: torch.Tensor) -> torch.Tensor:
         """The parent's static-map test plus the cars where they are NOW (row 0); > 0 means in collision."""
@@ -127,9 +121,4 @@ class opponent_racing_controller(racing_controller):
         base = racing_controller.cost_function(self, state, action, info)
         x, y = state[:, 0], state[:, 1]
         row = self.env._opp_table[info["t"]].to(state.device)  # [K, 4]: the cars where they are predicted to be at this step
-        pen = torch.zeros_like(x)
-        for j in range(row.shape[0]):  # in slot order, like the device
-            dx, dy = x - row[j, 0], y - row[j, 1]
-            d2 = dx * dx + dy * dy
-            pen = pen + torch.where(d2 <= row[j, 2], row[j, 3], torch.zeros_like(x))
-        return base + pen
+        return base + disc_penalty(row, x, y)
