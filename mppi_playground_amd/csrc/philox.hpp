@@ -69,13 +69,30 @@ __device__ __forceinline__ float bm_u1_fma(uint32_t a) {
 }
 __device__ __forceinline__ float bm_u1_mul(uint32_t a) { return (float)((a >> 8) + 1u) * (1.0f / 16777216.0f); }
 
+// The two factors of a normal, each a function of one operand alone: the radius of u1 and the cos / sin pair of the angle.
+// Accuracy: tests/test_gpu_noise_domain.py evaluates both on the device for EVERY operand (2^24 radii, 2^23 angles) against
+// float64 and holds their product, over all 2^47 pairs, to 1e-4 of a float64 Box-Muller of the same words — and each
+// factor to twice its measured error (profiles/noise_domain.md: 4.9e-7 on the radius, 1.3e-7 on cos / sin, per octave of u1).
+__device__ __forceinline__ float bm_radius(float u1) {
+    return __builtin_amdgcn_sqrtf(-1.38629436112f * __builtin_amdgcn_logf(u1));  // -2 ln2 log2(u1)
+}
+__device__ __forceinline__ float bm_cos(float rev) { return __builtin_amdgcn_cosf(rev); }
+__device__ __forceinline__ float bm_sin(float rev) { return __builtin_amdgcn_sinf(rev); }
+__device__ __forceinline__ void bm_trig(float rev, float& c, float& s) {
+    c = bm_cos(rev);
+    s = bm_sin(rev);
+}
+
+// (Each product is written next to its own factor, not after bm_trig: with both transcendentals ahead of both multiplies the
+// compiler schedules 140 kernels differently, scripts/device_asm_diff.py and profiles/noise_domain.md.  The test program
+// multiplies the two tables itself and holds both instantiations of box_muller to those products bit for bit.)
 template <bool U1_FMA = true>
 __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
     const float u1 = U1_FMA ? bm_u1_fma(a) : bm_u1_mul(a);
     const float rev = bm_angle(b);  // 1 + u2, in revolutions
-    const float rad = __builtin_amdgcn_sqrtf(-1.38629436112f * __builtin_amdgcn_logf(u1));  // -2 ln2 log2(u1)
-    z0 = rad * __builtin_amdgcn_cosf(rev);
-    z1 = rad * __builtin_amdgcn_sinf(rev);
+    const float rad = bm_radius(u1);
+    z0 = rad * bm_cos(rev);
+    z1 = rad * bm_sin(rev);
 }
 
 }  // namespace mppi
