@@ -63,7 +63,9 @@ enum {
     MPPI_MODEL_MLP41 = 7,       /* learned dynamics: a small MLP, 4 states, 1 control (mppi_set_mlp)  */
     MPPI_MODEL_MLP42 = 8,       /* the same with 2 controls                                           */
     MPPI_MODEL_NAV2D_DISCS = 9, /* MPPI_MODEL_NAV2D + up to MPPI_MAX_DISCS moving disc obstacles (mppi_set_discs) */
-    MPPI_MODEL_RACING_DISCS = 10 /* MPPI_MODEL_RACING + up to MPPI_MAX_DISCS moving disc obstacles: opponent cars (mppi_set_discs) */
+    MPPI_MODEL_RACING_DISCS = 10, /* MPPI_MODEL_RACING + up to MPPI_MAX_DISCS moving disc obstacles: opponent cars (mppi_set_discs) */
+    MPPI_MODEL_NAV2D_DISCS_SOFT = 11,  /* MPPI_MODEL_NAV2D_DISCS with a graded penalty skirt round every disc (mppi_set_disc_softness) */
+    MPPI_MODEL_RACING_DISCS_SOFT = 12  /* MPPI_MODEL_RACING_DISCS with the same skirt */
 };
 
 /* Racing parameter vector (mppi_set_model_params), racing_env.py:37-42,341-370, racing.py:41-46 */
@@ -234,6 +236,32 @@ int mppi_set_mlp(mppi_handle_t h, const float* table_host, int n_floats, int hid
  * [rows][8] layout, byte for byte.  mppi_model_step takes the id and runs racing's dynamics (the discs are cost only). */
 int mppi_set_discs(mppi_handle_t h, const float* discs, int rows, int n, int on_device, void* stream);
 int mppi_get_discs(mppi_handle_t h, float* out, int* rows_out, int* n_out, int on_device, void* stream);
+/* Soft moving discs: MPPI_MODEL_NAV2D_DISCS_SOFT / MPPI_MODEL_RACING_DISCS_SOFT are the two disc models above — same
+ * dynamics, parameters, maps, entry rules, reference window, step table and mppi_set_discs / mppi_get_discs — with a graded
+ * penalty SKIRT round every disc instead of the bare indicator.  Two launch-uniform numbers per handle describe it:
+ *     reach  rho, finite and > 1: the skirt ends at rho * r from the centre;
+ *     skirt  phi in [0, 1]: just outside the rim the penalty is phi * w (phi = 1: continuous; phi < 1: a collision stays
+ *            categorically worse than a near miss).
+ * With kappa = rho^2 the library forms two fp32 coefficients in double and rounds each once:
+ *     a = fl32(phi * kappa / (kappa - 1)),  b = fl32(phi / (kappa - 1))
+ * and charges disc j = 0..n-1 of row t in slot order.  At option "math" = 0 every operation rounds on its own, with the IEEE
+ * quotient:
+ *     dx = x - cx; dy = y - cy; d2 = dx*dx + dy*dy; q = d2 / r2; ramp = max(a - b*q, 0)
+ *     f = (d2 <= r2) ? 1 : ramp;  pen = pen + w*f
+ * The fast levels spell every fused operation out (every copy of the horizon loop forms the same bits):
+ *     d2 = fma(dx, dx, dy*dy); q = d2 * rcp(r2); ramp = max(fma(-b, q, a), 0); f = (d2 <= r2) ? 1 : ramp; pen = fma(w, f, pen)
+ * with rcp(r2) one v_rcp_f32 (1 ulp) on the device.  cost = base + pen, added last, as for the hard models.  The penalty is
+ * linear in d2 (not in d) from phi * w at the rim to 0 at d = rho * r, and w inside: the inside test is the hard rule's own
+ * compare, so with phi = 0 (a = b = 0) a soft model equals its hard model bit for bit at every math level.  Overlapping
+ * discs add up, padded slots are never reached, the terminal cost reads row T-1.  One (rho, phi) per handle, not per disc.
+ * On a soft handle mppi_set_discs also refuses a HOST table with r2 <= 0 in a real disc (MPPI_E_INVALID: the rule divides
+ * by r2); a device table is trusted as it is.
+ * mppi_set_disc_softness completes a lazily completed state sequence first and takes effect for the next launch; a soft
+ * handle starts at reach = 2, skirt = 1.  MPPI_E_INVALID on a handle of any other model, for reach not finite or <= 1 and
+ * for skirt outside [0, 1] or NaN.  mppi_get_disc_softness returns the pair as it was set (either pointer may be NULL).
+ * mppi_clone_state carries the pair.  mppi_model_step takes the two ids and runs nav2d's / racing's dynamics. */
+int mppi_set_disc_softness(mppi_handle_t h, float reach, float skirt);
+int mppi_get_disc_softness(mppi_handle_t h, float* reach, float* skirt);
 
 /* The racing control tick without the host (example/racing.py:73-81,161-218,221-266).
  *   mppi_set_center_path  `env.racing_center_path` [n][3] = (x, y, yaw) and the constants of

@@ -16,10 +16,10 @@ MODEL_GENERIC = -1
 MAX_DIM_CONTROL = 4           # controls held by MppiConfig
 MAX_DIM_CONTROL_GENERIC = 64  # opaque callables: any dim_control up to this
 MODEL_IDS = {"pendulum": 0, "cartpole": 1, "mountaincar": 2, "nav2d": 3, "racing": 4, "mjcartpole": 5, "goalzone": 6,
-             "mlp41": 7, "mlp42": 8, "nav2d_discs": 9, "racing_discs": 10}
+             "mlp41": 7, "mlp42": 8, "nav2d_discs": 9, "racing_discs": 10, "nav2d_discs_soft": 11, "racing_discs_soft": 12}
 MODEL_DIMS = {"pendulum": (2, 1), "cartpole": (4, 1), "mountaincar": (2, 1), "nav2d": (3, 2), "racing": (4, 2),
               "mjcartpole": (4, 1), "goalzone": (7, 2), "mlp41": (4, 1), "mlp42": (4, 2),
-              "nav2d_discs": (3, 2), "racing_discs": (4, 2)}
+              "nav2d_discs": (3, 2), "racing_discs": (4, 2), "nav2d_discs_soft": (3, 2), "racing_discs_soft": (4, 2)}
 MLP_HIDDEN = 32               # MPPI_MLP_HIDDEN
 MLP_ACTIVATIONS = {"relu": 0, "tanh": 1}  # MPPI_MLP_*
 MAX_DISCS = 8                 # MPPI_MAX_DISCS
@@ -45,7 +45,7 @@ SYMBOLS = [
     "mppi_set_action_cost", "mppi_set_action_cost_lambda", "mppi_add_action_cost",
     "mppi_set_noise_correlation", "mppi_get_noise_correlation",
     "mppi_set_mlp",
-    "mppi_set_discs", "mppi_get_discs",
+    "mppi_set_discs", "mppi_get_discs", "mppi_set_disc_softness", "mppi_get_disc_softness",
 ]
 
 
@@ -170,6 +170,8 @@ def load():
     lib.mppi_set_mlp.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     lib.mppi_set_discs.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.mppi_get_discs.argtypes = [vp, vp, vp, vp, i32, vp]
+    lib.mppi_set_disc_softness.argtypes = [vp, f32, f32]
+    lib.mppi_get_disc_softness.argtypes = [vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the .so does not export what the header declares
         if name not in ("mppi_version", "mppi_last_error"):

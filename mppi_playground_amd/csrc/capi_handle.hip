@@ -183,6 +183,7 @@ int mppi_create(const MppiConfig* cfg, mppi_handle_t* out) {
     HIP_TRY(h, se.lambda_dev.alloc(1));
     HIP_TRY(h, red.live_hint.alloc(1, true));
     std::memset(&h->model.ctx, 0, sizeof(h->model.ctx));
+    if (is_soft_discs(cfg->model)) apply_disc_softness(h, 2.0f, 1.0f);
     if (h->wide) {
         HIP_TRY(h, c.coltab.alloc(12 * (size_t)d.R));
         h->limits_set = false;
@@ -338,6 +339,7 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
         dm.ref_part_rows = sm.ref_part_rows; dm.disc_part_rows = sm.disc_part_rows;
         publish_step_table(dst);
     }
+    dm.soft_reach = sm.soft_reach; dm.soft_skirt = sm.soft_skirt;  // (the coefficients they stand for were copied with ctx)
     if (sm.mlp && sm.ctx.ref) {  // learned dynamics: the weight table, with the flags that ride in ref_rows
         if (dm.mlp.n != sm.mlp.n) HIP_TRY(dst, dm.mlp.alloc(sm.mlp.n));
         CLONE(model.mlp);

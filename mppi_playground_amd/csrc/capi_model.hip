@@ -115,6 +115,14 @@ __global__ __launch_bounds__(BLOCK) void disc_rows_strided_kernel(const float* _
     if (f < (size_t)rows * DISC_ROW) out[(f / DISC_ROW) * (size_t)stride + off + f % DISC_ROW] = disc_padded(discs, n, f);
 }
 
+// the soft disc models' skirt: keep the pair as it was given and form the two coefficients of the rule (mppi_discs.hpp) in
+// double, each rounded once
+void apply_disc_softness(mppi_handle_t h, float reach, float skirt) {
+    const double kappa = (double)reach * (double)reach, phi = (double)skirt;
+    h->model.soft_reach = reach; h->model.soft_skirt = skirt;
+    set_disc_soft(h->model.ctx, h->cfg.model, (float)(phi * kappa / (kappa - 1.0)), (float)(phi / (kappa - 1.0)));
+}
+
 }  // namespace mppi
 
 extern "C" {
@@ -278,6 +286,9 @@ int mppi_set_discs(mppi_handle_t h, const float* discs, int rows, int n, int on_
         for (size_t i = 0; i < in_floats; ++i)
             if (!std::isfinite(discs[i]) || (i % DISC_FLOATS == 3 && discs[i] < 0.0f))
                 return fail(h, MPPI_E_INVALID, "disc table: every value must be finite and every penalty >= 0");
+    if (!on_device && is_soft_discs(h->cfg.model))  // (the soft rule divides by r2)
+        for (size_t i = 2; i < in_floats; i += DISC_FLOATS)
+            if (!(discs[i] > 0.0f)) return fail(h, MPPI_E_INVALID, "disc table: a soft disc model needs r2 > 0 for every disc");
     hipStream_t s = (hipStream_t)stream;
     const StepLayout L = step_layout(h->cfg.model);
     if (int rc = reserve_step_table(h, rows)) return rc;
@@ -311,6 +322,24 @@ int mppi_get_discs(mppi_handle_t h, float* out, int* rows_out, int* n_out, int o
     HIP_TRY(h, copy_rows(out, DISC_ROW, h->model.ref.p + L.disc_off, L.stride, DISC_ROW, rows,
                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     if (!on_device) HIP_TRY(h, hipStreamSynchronize(s));
+    return MPPI_OK;
+}
+
+int mppi_set_disc_softness(mppi_handle_t h, float reach, float skirt) {
+    if (!h) return MPPI_E_INVALID;
+    if (!is_soft_discs(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the skirt belongs to the soft moving-disc models");
+    if (!std::isfinite(reach) || !(reach > 1.0f) || !(skirt >= 0.0f && skirt <= 1.0f))
+        return fail(h, MPPI_E_INVALID, "disc softness: reach finite and > 1, skirt in [0, 1]");
+    if (int rc = settle_state_seq(h)) return rc;  // a lazily completed state sequence belongs to the OLD constants: roll it out first
+    apply_disc_softness(h, reach, skirt);
+    return MPPI_OK;
+}
+
+int mppi_get_disc_softness(mppi_handle_t h, float* reach, float* skirt) {
+    if (!h) return MPPI_E_INVALID;
+    if (!is_soft_discs(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the skirt belongs to the soft moving-disc models");
+    if (reach) *reach = h->model.soft_reach;
+    if (skirt) *skirt = h->model.soft_skirt;
     return MPPI_OK;
 }
 
@@ -412,6 +441,8 @@ int mppi_model_step(int model, const float* params_host, int n_params, const flo
     case MPPI_MODEL_GOALZONE: CALL_STEP(MPPI_MODEL_GOALZONE); break;
     case MPPI_MODEL_NAV2D_DISCS: CALL_STEP(MPPI_MODEL_NAV2D_DISCS); break;  // (nav2d's dynamics: the discs are cost only)
     case MPPI_MODEL_RACING_DISCS: CALL_STEP(MPPI_MODEL_RACING); break;      // (racing's dynamics, racing's kernel)
+    case MPPI_MODEL_NAV2D_DISCS_SOFT: CALL_STEP(MPPI_MODEL_NAV2D); break;   // (nav2d's dynamics, nav2d's kernel)
+    case MPPI_MODEL_RACING_DISCS_SOFT: CALL_STEP(MPPI_MODEL_RACING); break;
     }
 #undef CALL_STEP
     return hipGetLastError() == hipSuccess ? MPPI_OK : MPPI_E_HIP;

@@ -53,4 +53,49 @@ MPPI_DISC_HOST_DEVICE float disc_row_penalty(const float* row, int n, float x, f
     return pen;
 }
 
+// ------------------------------------------------------------------------------------------------ the soft rule
+// The graded skirt of the soft disc models (include/mppi_hip.h, mppi_set_disc_softness, states the rule): inside the disc
+// (the hard rule's own compare, d2 <= r2) the penalty is w; outside it is w * max(a - b * d2 / r2, 0), linear in d2 from
+// skirt * w at the rim to 0 at reach * r.  a and b are the two launch-uniform coefficients the host formed from (reach, skirt).
+// FUSE = false: every operation rounds on its own, with the IEEE quotient, so a numpy fp32 restatement reproduces the bits.
+// FUSE = true: every fused operation is spelled out (fmaf), and the quotient is d2 * rcp(r2) — one v_rcp_f32 on the device,
+// 1.0f / r2 in a host build.  With a = b = 0 both forms return the hard rule's bits (f is 0 or 1, w * 1 is exact).
+MPPI_DISC_HOST_DEVICE float disc_rcp(float r2) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rcpf(r2);
+#else
+    return 1.0f / r2;
+#endif
+}
+
+// pen + w * (1 inside the disc, the ramp outside it)
+template <bool FUSE>
+MPPI_DISC_HOST_DEVICE float disc_add_soft(float pen, float x, float y, const Disc& k, float a, float b) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float d2 = disc_d2<FUSE>(x, y, k);
+    if (FUSE) {
+        const float q = d2 * disc_rcp(k.r2);
+        const float ramp = fmaxf(fmaf(-b, q, a), 0.0f);
+        return fmaf(k.w, d2 <= k.r2 ? 1.0f : ramp, pen);
+    }
+    const float q = d2 / k.r2;
+    const float bq = b * q;
+    const float ramp = fmaxf(a - bq, 0.0f);
+    const float wf = k.w * (d2 <= k.r2 ? 1.0f : ramp);
+    return pen + wf;
+}
+
+// the soft penalty of one row: discs 0 .. n-1 of `row`, in slot order
+template <bool FUSE>
+MPPI_DISC_HOST_DEVICE float disc_row_penalty_soft(const float* row, int n, float x, float y, float a, float b) {
+    float pen = 0.0f;
+    for (int j = 0; j < n; ++j) {
+        const Disc k = *reinterpret_cast<const Disc*>(row + DISC_FLOATS * j);
+        pen = disc_add_soft<FUSE>(pen, x, y, k, a, b);
+    }
+    return pen;
+}
+
 }  // namespace mppi

@@ -296,6 +296,7 @@ struct MppiSolver {
         DevBuf<float> ref;
         int ref_part_rows = 0;         // reference part: mppi_set_reference / mppi_ref_window
         int disc_part_rows = 0;        // disc part: mppi_set_discs
+        float soft_reach = 2.0f, soft_skirt = 1.0f;  // the soft disc models' skirt as it was set (mppi_set_disc_softness)
         DevBuf<float> mlp;             // weight table of the learned-dynamics models (mppi_set_mlp); ctx.ref points at it
         // device-resident reference window (mppi_set_center_path / mppi_ref_window)
         DevBuf<float> center8;         // [n][8] centre line with sin/cos of the yaw
@@ -374,11 +375,15 @@ inline bool model_dims(int model, ModelDims& md) {
     case MPPI_MODEL_MLP42: md = {4, 2}; return true;
     case MPPI_MODEL_NAV2D_DISCS: md = {3, 2}; return true;
     case MPPI_MODEL_RACING_DISCS: md = {4, 2}; return true;
+    case MPPI_MODEL_NAV2D_DISCS_SOFT: md = {3, 2}; return true;
+    case MPPI_MODEL_RACING_DISCS_SOFT: md = {4, 2}; return true;
     }
     return false;
 }
-// nav2d and its moving-disc variant: one set of dynamics, parameters, maps and host-checked preconditions
-inline bool is_nav2d(int model) { return model == MPPI_MODEL_NAV2D || model == MPPI_MODEL_NAV2D_DISCS; }
+// nav2d and its moving-disc variants: one set of dynamics, parameters, maps and host-checked preconditions
+inline bool is_nav2d(int model) {
+    return model == MPPI_MODEL_NAV2D || model == MPPI_MODEL_NAV2D_DISCS || model == MPPI_MODEL_NAV2D_DISCS_SOFT;
+}
 // parameters the dynamics of `model` read (the models without any take none)
 inline int model_param_count(int model) {
     return is_racing_model(model) ? MPPI_RP_COUNT : is_nav2d(model) ? MPPI_NP_COUNT
@@ -501,6 +506,8 @@ inline int math_level(mppi_handle_t h) { return use_fast(h) ? (h->opt.math_fast 
         MPPI_DISPATCH_NOHW(MPPI_MODEL_MLP42, CALL)                                                    \
         MPPI_DISPATCH_HW(MPPI_MODEL_NAV2D_DISCS, CALL)                                                \
         MPPI_DISPATCH_HW(MPPI_MODEL_RACING_DISCS, CALL)                                               \
+        MPPI_DISPATCH_HW(MPPI_MODEL_NAV2D_DISCS_SOFT, CALL)                                           \
+        MPPI_DISPATCH_HW(MPPI_MODEL_RACING_DISCS_SOFT, CALL)                                          \
         }                                                                                             \
     } while (0)
 
@@ -563,6 +570,7 @@ void refresh_pad(mppi_handle_t h, hipStream_t s);
 int prepare_map(mppi_handle_t h, int slot, int nx, int ny, float cell, float ox, float oy);
 int reserve_step_table(mppi_handle_t h, int rows);
 void publish_step_table(mppi_handle_t h);
+void apply_disc_softness(mppi_handle_t h, float reach, float skirt);
 
 // the per-column sigma table the sampler reads (see MppiSolver::Cov)
 inline float* sigma_table(mppi_handle_t h) { return h->wide ? h->core.coltab.p : h->cov.sigtab.p; }

@@ -80,7 +80,11 @@ constexpr int RACING_REF_ROW = 8;                            // floats of a raci
 constexpr int RACING_DISCS_KROW = RACING_REF_ROW + DISC_ROW;  // 40
 constexpr int RACING_DISCS_SLOT = MPPI_RP_COUNT;              // P[] slot of the disc count
 static_assert(RACING_DISCS_SLOT < MPPI_MAX_PARAMS, "the disc count needs a free parameter slot");
-constexpr bool is_racing_model(int model) { return model == MPPI_MODEL_RACING || model == MPPI_MODEL_RACING_DISCS; }
+constexpr bool is_racing_model(int model) {
+    return model == MPPI_MODEL_RACING || model == MPPI_MODEL_RACING_DISCS || model == MPPI_MODEL_RACING_DISCS_SOFT;
+}
+// the soft disc models (mppi_set_disc_softness): the hard models' table, staging and count, a graded skirt in the cost
+constexpr bool is_soft_discs(int model) { return model == MPPI_MODEL_NAV2D_DISCS_SOFT || model == MPPI_MODEL_RACING_DISCS_SOFT; }
 struct StepLayout {
     int stride;      // floats per step row (0: the model has no step table)
     int ref_floats;  // the reference part is floats [0, ref_floats) (0: none)
@@ -92,6 +96,8 @@ constexpr StepLayout step_layout(int model) {
     return model == MPPI_MODEL_RACING         ? StepLayout{RACING_REF_ROW, RACING_REF_ROW, -1}
            : model == MPPI_MODEL_NAV2D_DISCS  ? StepLayout{DISC_ROW, 0, 0}
            : model == MPPI_MODEL_RACING_DISCS ? StepLayout{RACING_DISCS_KROW, RACING_REF_ROW, RACING_REF_ROW}
+           : model == MPPI_MODEL_NAV2D_DISCS_SOFT  ? StepLayout{DISC_ROW, 0, 0}
+           : model == MPPI_MODEL_RACING_DISCS_SOFT ? StepLayout{RACING_DISCS_KROW, RACING_REF_ROW, RACING_REF_ROW}
                                               : StepLayout{0, 0, -1};
 }
 static_assert(step_layout(MPPI_MODEL_RACING_DISCS).disc_off % 4 == 0 && step_layout(MPPI_MODEL_RACING_DISCS).stride % 4 == 0,
@@ -103,16 +109,24 @@ constexpr int ref_stride(int model) { return step_layout(model).stride; }
 constexpr int disc_offset(int model) { return step_layout(model).disc_off; }
 // The number of discs per row: the one accessor both disc models go through (`model`: a constant where a kernel calls it)
 MPPI_HD int disc_count(const ModelCtx& c, int model = MPPI_MODEL_NAV2D_DISCS) {
-    if (model != MPPI_MODEL_RACING_DISCS) return c.tan_small;
+    if (!is_racing_model(model)) return c.tan_small;
     int32_t n;
     __builtin_memcpy(&n, &c.P[RACING_DISCS_SLOT], sizeof(n));
     return n;
 }
 inline void set_disc_count(ModelCtx& c, int model, int n) {
-    if (model != MPPI_MODEL_RACING_DISCS) { c.tan_small = n; return; }
+    if (!is_racing_model(model)) { c.tan_small = n; return; }
     const int32_t v = n;
     __builtin_memcpy(&c.P[RACING_DISCS_SLOT], &v, sizeof(v));
 }
+// The two coefficients {a, b} of the soft rule (mppi_discs.hpp) ride in free P[] slots too, which mppi_set_model_params does
+// not write: behind nav2d's parameters, and behind racing's disc count
+constexpr int soft_slot(int model) { return is_racing_model(model) ? RACING_DISCS_SLOT + 1 : MPPI_NP_COUNT; }
+static_assert(soft_slot(MPPI_MODEL_NAV2D_DISCS_SOFT) + 1 < MPPI_MAX_PARAMS && soft_slot(MPPI_MODEL_RACING_DISCS_SOFT) + 1 < MPPI_MAX_PARAMS,
+              "the soft coefficients need two free parameter slots");
+struct DiscSoft { float a, b; };
+MPPI_HD DiscSoft disc_soft(const ModelCtx& c, int model) { return DiscSoft{c.P[soft_slot(model)], c.P[soft_slot(model) + 1]}; }
+inline void set_disc_soft(ModelCtx& c, int model, float a, float b) { c.P[soft_slot(model)] = a; c.P[soft_slot(model) + 1] = b; }
 
 // Host-side plan of the padded grid.  The models clamp positions to [xlo, xhi] x [ylo, yhi]; if every index
 // round(p/cell + origin) reachable under that clamp lies in [0, nx] x [0, ny], the lookup needs no bounds test.
@@ -237,6 +251,7 @@ constexpr bool krow_is_stride() { return ModelT<MODEL, 0>::KROW == step_layout(M
 static_assert(krow_is_stride<MPPI_MODEL_PENDULUM>() && krow_is_stride<MPPI_MODEL_CARTPOLE>() && krow_is_stride<MPPI_MODEL_MOUNTAINCAR>() &&
               krow_is_stride<MPPI_MODEL_NAV2D>() && krow_is_stride<MPPI_MODEL_RACING>() && krow_is_stride<MPPI_MODEL_MJCARTPOLE>() &&
               krow_is_stride<MPPI_MODEL_GOALZONE>() && krow_is_stride<MPPI_MODEL_MLP41>() && krow_is_stride<MPPI_MODEL_MLP42>() &&
-              krow_is_stride<MPPI_MODEL_NAV2D_DISCS>() && krow_is_stride<MPPI_MODEL_RACING_DISCS>(),
+              krow_is_stride<MPPI_MODEL_NAV2D_DISCS>() && krow_is_stride<MPPI_MODEL_RACING_DISCS>() &&
+              krow_is_stride<MPPI_MODEL_NAV2D_DISCS_SOFT>() && krow_is_stride<MPPI_MODEL_RACING_DISCS_SOFT>(),
               "a functor's KROW is the stride of step_layout(model)");
 }  // namespace mppi

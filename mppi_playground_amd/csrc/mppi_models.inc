@@ -639,6 +639,33 @@ struct Model<MPPI_MODEL_RACING_DISCS, FAST> : Model<MPPI_MODEL_RACING, FAST> {
     }
 };
 
+// The soft disc models (include/mppi_hip.h, mppi_set_disc_softness, states the rule; mppi_discs.hpp is the arithmetic): the
+// hard models with a graded skirt round every disc.  Step table, K, KROW, load_k, LDS staging and the entry rules are
+// inherited; only cost() differs — the same base cost, the soft row penalty with the two launch-uniform coefficients
+// (disc_soft), added last.
+template <bool FAST>
+struct Model<MPPI_MODEL_NAV2D_DISCS_SOFT, FAST> : Model<MPPI_MODEL_NAV2D_DISCS, FAST> {
+    using Hard = Model<MPPI_MODEL_NAV2D_DISCS, FAST>;
+    static MPPI_HD float cost(const ModelCtx& c, const typename Hard::K& k, const float* s, const float* u, const float* pu, bool& bad,
+                              bool general = false) {
+        const float base = Hard::Base::cost(c, NoStepConst{}, s, u, pu, bad, general);
+        const DiscSoft f = disc_soft(c, MPPI_MODEL_NAV2D_DISCS_SOFT);
+        const float pen = disc_row_penalty_soft<FAST>(k.row, disc_count(c, MPPI_MODEL_NAV2D_DISCS_SOFT), s[0], s[1], f.a, f.b);
+        return base + pen;
+    }
+};
+template <bool FAST>
+struct Model<MPPI_MODEL_RACING_DISCS_SOFT, FAST> : Model<MPPI_MODEL_RACING_DISCS, FAST> {
+    using Hard = Model<MPPI_MODEL_RACING_DISCS, FAST>;
+    static MPPI_HD float cost(const ModelCtx& c, const typename Hard::K& k, const float* s, const float* u, const float* pu, bool& bad,
+                              bool general = false) {
+        const float base = Hard::Base::cost(c, k.ref, s, u, pu, bad, general);
+        const DiscSoft f = disc_soft(c, MPPI_MODEL_RACING_DISCS_SOFT);
+        const float pen = disc_row_penalty_soft<FAST>(k.discs, disc_count(c, MPPI_MODEL_RACING_DISCS_SOFT), s[0], s[1], f.a, f.b);
+        return base + pen;
+    }
+};
+
 // Learned dynamics: a multi-layer perceptron whose weights are data (include/mppi_hip.h, mppi_set_mlp, states the
 // arithmetic; the table is ctx.ref, the flags ctx.ref_rows).  Every product-sum is written a * b + c: mppi::strict rounds
 // each operation on its own (the numpy restatement of tests/mlp_ref.py, bit for bit with relu), the fast namespaces may

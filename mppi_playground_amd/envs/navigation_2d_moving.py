@@ -20,7 +20,7 @@ from typing import Tuple
 
 import torch
 
-from envs.discs import MAX_DISCS, disc_hits, disc_penalty
+from envs.discs import MAX_DISCS, check_softness, disc_hits, disc_penalty, soft_coefficients, soft_disc_penalty
 from envs.navigation_2d import Navigation2DEnv, _nav_inputs
 from pi_mpc.native import native_model
 
@@ -104,3 +104,56 @@ class MovingObstacleNav2DEnv(Navigation2DEnv):
         """The parent's static-map test plus the discs where they are NOW (row 0); > 0 means in collision."""
         hit = super().collision_check(state)
         return hit + disc_hits(self._disc_table[0], state).to(hit.dtype).reshape(hit.shape)
+
+
+def _soft_moving_inputs(env: "SoftMovingObstacleNav2DEnv") -> dict:
+    spec = dict(_moving_inputs(env))
+    spec["discs"] = dict(spec["discs"], soft={"reach": env.soft_reach, "skirt": env.soft_skirt})
+    return spec
+
+
+class SoftMovingObstacleNav2DEnv(MovingObstacleNav2DEnv):
+    """MovingObstacleNav2DEnv with a graded penalty SKIRT round every disc instead of the bare indicator: w inside a disc as
+    before, outside it a ramp, linear in the squared distance, from `soft_skirt` * w at the rim to 0 at `soft_reach` * radius
+    (include/mppi_hip.h, mppi_set_disc_softness, states the arithmetic) — so that a sample that keeps its distance is cheaper
+    than one that grazes a rim.  One (reach, skirt) for all discs.  Tagged "nav2d_discs_soft"; every radius must be > 0.
+    collision_check stays the hard test."""
+
+    def __init__(self, horizon: int, soft_reach: float = 2.0, soft_skirt: float = 1.0, device=torch.device("cuda"),
+                 dtype=torch.float32, seed: int = 42, native_step: bool = True) -> None:
+        self.set_softness(soft_reach, soft_skirt)
+        super().__init__(horizon, device=device, dtype=dtype, seed=seed, native_step=native_step)
+
+    def set_softness(self, reach: float, skirt: float) -> None:
+        """reach finite and > 1, skirt in [0, 1] (ValueError otherwise); takes effect with the next solve."""
+        self._soft_reach, self._soft_skirt = check_softness(reach, skirt)
+        self._soft_ab = soft_coefficients(self._soft_reach, self._soft_skirt)
+
+    @property
+    def soft_reach(self) -> float:
+        return self._soft_reach
+
+    @property
+    def soft_skirt(self) -> float:
+        return self._soft_skirt
+
+    def set_moving_obstacles(self, pos, vel, radius, weight=None) -> None:
+        """As the parent's, and every radius > 0 (the ramp divides by the squared radius)."""
+        r = torch.as_tensor(radius, dtype=torch.float64)
+        if torch.as_tensor(pos).numel() and not bool((r > 0).all()):
+            raise ValueError("soft moving obstacles: every radius must be > 0")
+        super().set_moving_obstacles(pos, vel, radius, weight)
+
+    @native_model("nav2d_discs_soft", "dynamics", _soft_moving_inputs)
+    def dynamics(self, state: torch.Tensor, action: torch.Tensor, delta_t: float = 0.1) -> torch.Tensor:
+        return Navigation2DEnv.dynamics(self, state, action, delta_t)
+
+    @native_model("nav2d_discs_soft", "cost", _soft_moving_inputs)
+    def cost_function(self, state: torch.Tensor, action: torch.Tensor, info: dict) -> torch.Tensor:
+        # the parent's base cost, operation by operation (see MovingObstacleNav2DEnv.cost_function), then the soft penalty
+        x, y = state[:, 0], state[:, 1]
+        gx, gy = x - self._goal_pos[0], y - self._goal_pos[1]
+        goal_cost = torch.sqrt((gx * gx + gy * gy).double()).to(state.dtype)
+        occ = self._obstacle_map.compute_cost(state[:, :2].unsqueeze(1)).squeeze(1)
+        base = goal_cost + self.obstacle_weight * occ
+        return base + soft_disc_penalty(self._disc_table[info["t"]], x, y, *self._soft_ab)

@@ -77,7 +77,7 @@ class racing_controller:
         the same stream; otherwise the host statement of calc_ref_trajectory below runs."""
         T = self.solver._horizon
         if (self.device_tick and torch.is_tensor(state) and state.is_cuda and torch.is_tensor(racing_center_path)
-                and getattr(self.solver, "_model", None) in ("racing", "racing_discs")):
+                and getattr(self.solver, "_model", None) in ("racing", "racing_discs", "racing_discs_soft")):
             key = (racing_center_path, racing_center_path._version)
             held = self._center_on_device
             if held is None or held[0] is not key[0] or held[1] != key[1]:

@@ -20,7 +20,7 @@ from typing import Tuple
 
 import torch
 
-from envs.discs import MAX_DISCS, disc_hits, disc_penalty
+from envs.discs import MAX_DISCS, check_softness, disc_hits, disc_penalty, soft_coefficients, soft_disc_penalty
 from envs.racing_controller import _racing_cost_inputs, racing_controller
 from envs.racing_env import RacingEnv, _racing_dyn_inputs
 from pi_mpc.native import native_model
@@ -122,3 +122,56 @@ class opponent_racing_controller(racing_controller):
         x, y = state[:, 0], state[:, 1]
         row = self.env._opp_table[info["t"]].to(state.device)  # [K, 4]: the cars where they are predicted to be at this step
         return base + disc_penalty(row, x, y)
+
+
+class SoftOpponentRacingEnv(OpponentRacingEnv):
+    """OpponentRacingEnv whose cars carry a graded penalty SKIRT (include/mppi_hip.h, mppi_set_disc_softness): w inside a car's
+    disc as before, outside it a ramp, linear in the squared distance, from `soft_skirt` * w at the rim to 0 at `soft_reach` *
+    radius.  One (reach, skirt) for all cars; every radius must be > 0.  The pair lives here; soft_opponent_racing_controller's
+    cost reads it.  Tagged "racing_discs_soft"; collision_check stays the hard test."""
+
+    def __init__(self, horizon: int = 25, soft_reach: float = 2.0, soft_skirt: float = 1.0, device=torch.device("cuda"),
+                 dtype=torch.float32, seed: int = 42, native_step: bool = True) -> None:
+        self.set_softness(soft_reach, soft_skirt)
+        super().__init__(horizon, device=device, dtype=dtype, seed=seed, native_step=native_step)
+
+    def set_softness(self, reach: float, skirt: float) -> None:
+        """reach finite and > 1, skirt in [0, 1] (ValueError otherwise); takes effect with the next solve."""
+        self._soft_reach, self._soft_skirt = check_softness(reach, skirt)
+        self._soft_ab = soft_coefficients(self._soft_reach, self._soft_skirt)
+
+    @property
+    def soft_reach(self) -> float:
+        return self._soft_reach
+
+    @property
+    def soft_skirt(self) -> float:
+        return self._soft_skirt
+
+    def set_opponents(self, path_index, speed, radius, lateral_offset=0.0, weight=None) -> None:
+        """As the parent's, and every radius > 0 (the ramp divides by the squared radius)."""
+        r = torch.as_tensor(radius, dtype=torch.float64)
+        if torch.as_tensor(path_index).numel() and not bool((r > 0).all()):
+            raise ValueError("soft opponent cars: every radius must be > 0")
+        super().set_opponents(path_index, speed, radius, lateral_offset, weight)
+
+    @native_model("racing_discs_soft", "dynamics", _racing_dyn_inputs)
+    def dynamics(self, state: torch.Tensor, action: torch.Tensor, delta_t: float = 0.1) -> torch.Tensor:
+        return RacingEnv.dynamics(self, state, action, delta_t)
+
+
+def _soft_opponent_cost_inputs(ctrl: "soft_opponent_racing_controller") -> dict:
+    spec = dict(_opponent_cost_inputs(ctrl))
+    spec["discs"] = dict(spec["discs"], soft={"reach": ctrl.env.soft_reach, "skirt": ctrl.env.soft_skirt})
+    return spec
+
+
+class soft_opponent_racing_controller(opponent_racing_controller):
+    """opponent_racing_controller over a SoftOpponentRacingEnv: the same tick, the cost with the cars' skirts."""
+
+    @native_model("racing_discs_soft", "cost", _soft_opponent_cost_inputs)
+    def cost_function(self, state: torch.Tensor, action: torch.Tensor, info: dict) -> torch.Tensor:
+        base = racing_controller.cost_function(self, state, action, info)
+        x, y = state[:, 0], state[:, 1]
+        row = self.env._opp_table[info["t"]].to(state.device)  # [K, 4]: the cars where they are predicted to be at this step
+        return base + soft_disc_penalty(row, x, y, *self.env._soft_ab)

@@ -588,6 +588,12 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             if getattr(self._h, "discs_key", None) != key:  # (kept on the handle, like the weight table's)
                 self._put_discs(discs["table"])
                 self._h.discs_key = key
+            soft = discs.get("soft")
+            if soft is not None:  # the soft disc models: the skirt travels whenever the pair changed
+                pair = (float(soft["reach"]), float(soft["skirt"]))
+                if getattr(self._h, "soft_key", None) != pair:  # (a new handle starts at the library's default: told once)
+                    self._h.call("mppi_set_disc_softness", *pair)
+                    self._h.soft_key = pair
         for slot, grid in enumerate(spec.get("maps", ())):
             key = (id(grid.cells), grid.version)
             if self._uploaded.get(slot) != key:

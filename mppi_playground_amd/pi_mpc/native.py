@@ -11,10 +11,13 @@ where `provider(owner)` returns the model's current inputs as plain host data:
     {"params": [floats], "maps": [GridSpec, ...], "ref_path": ndarray[rows,4] | None,
      "mlp": {"table": float32[n], "hidden_layers": 1 | 2, "activation": "relu" | "tanh", "residual": bool, "version": int},
      "discs": {"table": float32 [rows, n, 4] = {cx, cy, r2, w} per horizon step (a torch tensor on the solver's device, or
-               an ndarray), "version": int}}
+               an ndarray), "version": int,
+               "soft": {"reach": float > 1, "skirt": float in [0, 1]}  (the soft disc models only)}}
 ("mlp": the learned-dynamics models only; "discs": the moving-disc models only — "nav2d_discs" (envs.MovingObstacleNav2DEnv)
 and "racing_discs" (envs.racing_opponents: opponent cars, next to racing's "ref_path" or device-built window) — rows >= the
-horizon and n <= 8 or the solver raises ValueError; either table is uploaded again when its `version` changes.)
+horizon and n <= 8 or the solver raises ValueError; either table is uploaded again when its `version` changes.  "soft": the
+graded skirt of "nav2d_discs_soft" / "racing_discs_soft" (envs.SoftMovingObstacleNav2DEnv, envs.racing_opponents'
+Soft classes); the solver hands the pair to mppi_set_disc_softness before a solve whenever it changed.)
 `owner` is the bound method's `__self__` (None for plain functions).  The solver calls the provider
 of the cost callable before every solve (the racing reference window changes every tick,
 example/racing.py:73-81) and re-uploads only what changed.
