@@ -440,6 +440,61 @@ int mppi_add_action_cost(mppi_handle_t h, float lambda /* >= 0, or MPPI_LAMBDA_D
  *   mppi_get_noise_correlation  the current beta [dim_control] (zeros while off). */
 int mppi_set_noise_correlation(mppi_handle_t h, const float* beta_host /* [dim_control]; NULL or all zero: off */);
 int mppi_get_noise_correlation(mppi_handle_t h, float* beta_out_host);
+/* Risk-aware solves: every sample is rolled out from a SET of start states ("particles": a filter's particles, draws from a
+ * mean and a covariance) and its P costs are folded into one by a risk measure.  Opt-in; with no particles set nothing changes,
+ * bit for bit, and nothing else is launched.  The noise identity of a sample, (seed, solve, i, t, k), does not depend on the
+ * start state: the cost of particle m for sample i is what a plain handle computes from x0 = particles[m] with the same seed,
+ * solve index and mean — the same lane_cost, decided per particle (a start outside the position clamp, racing's unit wheel
+ * base, the library-math redo of a lane that left a fast path).
+ *   mppi_set_particles   particles [P][dim_state] fp32, 0 <= P <= MPPI_MAX_PARTICLES; P = 0 or a null pointer switches the
+ *                        feature off.  A host table (on_device = 0) is checked for finite values, staged and copied in stream
+ *                        order with no host wait, like mppi_set_reference's window; a device table is copied device-to-device
+ *                        on `stream` and trusted.  May be called before every solve.  A pending lazily completed state
+ *                        sequence is completed first (the particle launch does not carry the rider block).  The [P][N] cost
+ *                        matrix is allocated on first use and grows, blocking, on this set-up path only.  A generic handle
+ *                        accepts the call and only records P (for mppi_set_particle_costs).  MPPI_E_INVALID with option
+ *                        "mapping" = 1 (and that option is refused while particles are set).
+ *   mppi_get_particles   the table (out may be NULL to query P only); host copies synchronise.
+ *   mppi_set_risk        mode = MPPI_RISK_MEAN (default) | MPPI_RISK_WORST | MPPI_RISK_CVAR, k = the number of worst particles
+ *                        averaged under CVAR.  k is checked against P where the fold is launched (under CVAR: MPPI_E_INVALID
+ *                        for k < 1 or k > P), so either call may come first.
+ *   mppi_get_particle_costs  the [P][N] matrix of the last rollout (row m: the costs from particle m).
+ *   mppi_set_particle_costs  replaces the matrix and folds it: for the matrix what mppi_set_costs is for the vector (tests, and
+ *                        the generic path: one pass of the user's loops per particle); the minimum key is the fold's.
+ * The fold, for sample i with c[m] the cost from particle m — every operation rounds on its own in fp32 at every math level,
+ * the division is the IEEE quotient:
+ *     MEAN     a = c[0]; for m = 1..P-1: a = a + c[m];            cost = a / (float)P
+ *     WORST    cost = max over m of c[m]
+ *     CVAR(k)  c_(0) >= c_(1) >= ... the c[m] from largest to smallest (ties are interchangeable);
+ *              a = c_(0); for j = 1..k-1: a = a + c_(j);          cost = a / (float)k
+ * With P = 1 every mode returns c[0] unchanged (x / 1.0f).  CVAR(P) is the descending-order mean: the same set of addends as
+ * MEAN in another order, so the two need not agree to the bit.  A NaN among the c[m] makes the folded cost NaN in every mode
+ * (the ordering network would otherwise drop it); the minimum key then treats it as the plain rollout treats a NaN cost.
+ * One kernel, particle_fold_kernel: a lane per sample (at most 1024 blocks, which stride over larger problems), the P values of
+ * a sample in registers, a fixed compare-exchange network; it writes costs[i] and accumulates the shard minimum into the
+ * double-buffered minimum key exactly as the rollout does (no memset).
+ * While particles are set:
+ *   mppi_rollout_cost    launches rollout_particles_kernel — a wave walks one tile from one particle, grid ceil(tiles/4) x P —
+ *                        and then the fold.  Everything downstream (minimum, temperature rules, weights, queries,
+ *                        mppi_get_costs, the covariance adaptation) sees the folded cost.  The snapshots a rollout takes are
+ *                        the NOMINAL state (mppi_set_state / mppi_bind_state) and the mean: later re-rolls (mppi_top_samples,
+ *                        mppi_rollout_samples) and mppi_finalize's state sequence start from the nominal state — the particles
+ *                        decide costs only.  Regenerated noise and materialised tiles (colored noise, covariance adaptation,
+ *                        injected noise) both work.  The control-cost term does not depend on the state: with
+ *                        mppi_set_action_cost on, the particle rollout runs WITHOUT it and mppi_add_action_cost adds
+ *                        kappa * A_i once, AFTER the fold (fold first, then the term: cost_i = fold_i + kappa * A_i).
+ *   mppi_solve           takes the multi-kernel sequence; mppi_fused_geometry reports 0 / 0.
+ *   sharded handles      need nothing new (costs are local to a shard); every rank must be given the same particles.
+ * mppi_clone_state copies the table, P, the mode, k and the last matrix.  Stage 1 of mppi_get_timing covers the rollout plus the
+ * fold (events on the two dispatches). */
+#define MPPI_MAX_PARTICLES 16
+enum { MPPI_RISK_MEAN = 0, MPPI_RISK_WORST = 1, MPPI_RISK_CVAR = 2 };
+int mppi_set_particles(mppi_handle_t h, const float* particles, int P, int on_device, void* stream);
+int mppi_get_particles(mppi_handle_t h, float* out, int* P_out, int on_device, void* stream);
+int mppi_set_risk(mppi_handle_t h, int mode, int k);
+int mppi_get_risk(mppi_handle_t h, int* mode_out, int* k_out);
+int mppi_get_particle_costs(mppi_handle_t h, float* out /* [P][N] */, int on_device, void* stream);
+int mppi_set_particle_costs(mppi_handle_t h, const float* src /* [P][N] */, int on_device, void* stream);
 /* Lazily completed state sequences (mppi_set_option("lazy_state_seq", 1)).  The reference returns `state_seq` — the batch-1
  * rollout of the solution, mppi.py:448-449,508-524 — with the action sequence, but nothing on a control loop's critical
  * path needs it: the next solve samples around the mean, env.step applies a[0].  With the option set, mppi_finalize /

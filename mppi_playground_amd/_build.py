@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libmppi_hip.so")
 SOURCES = ["capi_handle.hip", "capi_model.hip", "capi_solve.hip", "capi_search.hip", "capi_topk.hip", "capi_exchange.hip",
-           "capi_covariance.hip", "capi_colored.hip"]
+           "capi_covariance.hip", "capi_colored.hip", "capi_particles.hip"]
 HEADER = os.path.join(HERE, "..", "include", "mppi_hip.h")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-slp-vectorize",
          "-fhip-fp32-correctly-rounded-divide-sqrt"]

@@ -23,6 +23,8 @@ MODEL_DIMS = {"pendulum": (2, 1), "cartpole": (4, 1), "mountaincar": (2, 1), "na
 MLP_HIDDEN = 32               # MPPI_MLP_HIDDEN
 MLP_ACTIVATIONS = {"relu": 0, "tanh": 1}  # MPPI_MLP_*
 MAX_DISCS = 8                 # MPPI_MAX_DISCS
+MAX_PARTICLES = 16            # MPPI_MAX_PARTICLES
+RISK_MODES = {"mean": 0, "worst": 1, "cvar": 2}  # MPPI_RISK_*
 SUMMARY_HEAD = 4
 LAMBDA_DEVICE = -1.0  # MPPI_LAMBDA_DEVICE: "the temperature a device-resident rule left on the device"
 AUTO_RULES = {None: 0, "ESSPS": 1, "LBPS": 2, "MPO": 3}  # MPPI_AUTO_*
@@ -46,6 +48,8 @@ SYMBOLS = [
     "mppi_set_noise_correlation", "mppi_get_noise_correlation",
     "mppi_set_mlp",
     "mppi_set_discs", "mppi_get_discs", "mppi_set_disc_softness", "mppi_get_disc_softness",
+    "mppi_set_particles", "mppi_get_particles", "mppi_set_risk", "mppi_get_risk", "mppi_get_particle_costs",
+    "mppi_set_particle_costs",
 ]
 
 
@@ -172,6 +176,12 @@ def load():
     lib.mppi_get_discs.argtypes = [vp, vp, vp, vp, i32, vp]
     lib.mppi_set_disc_softness.argtypes = [vp, f32, f32]
     lib.mppi_get_disc_softness.argtypes = [vp, vp, vp]
+    lib.mppi_set_particles.argtypes = [vp, vp, i32, i32, vp]
+    lib.mppi_get_particles.argtypes = [vp, vp, vp, i32, vp]
+    lib.mppi_set_risk.argtypes = [vp, i32, i32]
+    lib.mppi_get_risk.argtypes = [vp, vp, vp]
+    lib.mppi_get_particle_costs.argtypes = [vp, vp, i32, vp]
+    lib.mppi_set_particle_costs.argtypes = [vp, vp, i32, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the .so does not export what the header declares
         if name not in ("mppi_version", "mppi_last_error"):

@@ -277,6 +277,7 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
     if (src->color.on || dst->color.on)
         if (int rc = mppi_set_noise_correlation(dst, src->color.on ? src->color.beta.data() : nullptr)) return rc;
     dst->ac = src->ac;  // the control-cost term: switch, weight and the temperature of the next stand-alone rollout
+    if (int rc = clone_particles(dst, src)) return rc;  // risk-aware solves: table, count, risk measure, the last matrix
     CLONE(core.mean);
     CLONE(core.mean_used);
     CLONE(reduce.solve_stats);
@@ -389,6 +390,7 @@ int mppi_set_option(mppi_handle_t h, const char* key, int64_t value) {
     if (k == "timing") { h->timers.mode = (int)value; return MPPI_OK; }
     if (k == "timing_source") { h->timers.source = value ? 1 : 0; return MPPI_OK; }  // 1: events for every stage (A/B of the stamps)
     if (k == "mapping" && value && h->ac.on) return fail(h, MPPI_E_INVALID, "the control-cost term is not available with mapping = 1");
+    if (k == "mapping" && value && h->part.P > 0) return fail(h, MPPI_E_INVALID, "particles are not available with mapping = 1");
     if (k == "mapping") { o.mapping = value ? 1 : 0; return MPPI_OK; }
     if (k == "essps_cold") {  // the next ESSPS search (device chain and host loop) starts from the geometric grid
         h->search.essps_lo = h->search.essps_hi = 0.0;

@@ -161,6 +161,7 @@ static constexpr int64_t FUSED_AUTO_MAX_SAMPLES_SEARCH = 16384;  // ESSPS / LBPS
 static bool fused_applies(mppi_handle_t h, float lambda) {
     if (!h->opt.fused_mode || h->cfg.model == MPPI_MODEL_GENERIC || h->opt.mapping != 0) return false;
     if (h->ac.on) return false;  // the control-cost term lives in the multi-kernel rollout only (like the covariance adaptation)
+    if (h->part.P > 0) return false;  // ... and so does the rollout from a set of start states (mppi_set_particles)
     // measured (profiles/r03_experiments.md, r03_visitD_fused_crossover.txt): a cell round trip costs about as much as a
     // kernel boundary, so the single launch wins where it replaces more kernel boundaries than it needs round trips — with
     // a fixed temperature up to a few thousand samples (27 vs 32 us for racing at N = 1024, 29 vs 32 at 4096, 33 vs 32 at
@@ -302,6 +303,7 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
     if (int rc = check_ready(h)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (h->ac.on && h->opt.mapping == 1) return fail(h, MPPI_E_INVALID, "the control-cost term is not available with mapping = 1");
+    if (h->part.P > 0) return rollout_particles(h, s);  // risk-aware solves: every sample from every particle, then the fold
     if (h->opt.mapping == 1) {  // comparison variant: one wavefront per trajectory, reference-layout noise
         if (int rc = flush_state_seq(h, s)) return rc;
         if (!h->core.noise_std) HIP_TRY(h, h->core.noise_std.alloc((size_t)h->d.N * h->d.row));

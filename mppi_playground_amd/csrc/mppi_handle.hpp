@@ -16,6 +16,8 @@
 //   capi_exchange.hip  RCCL loader, comm / p2p exchanges, time-out flags             (+ the p2p kernels)
 //   capi_covariance.hip  covariance adaptation: settings, the per-step sigma table, the step after the weights (mppi_variance.hpp)
 //   capi_colored.hip   temporally correlated noise: the setting, its per-column table, the filtered draws (mppi_sample.hpp)
+//   capi_particles.hip risk-aware solves: the particle table, the risk measure, the rollout from every particle and the fold
+//                      (mppi_particles.hpp: rollout_particles_kernel, particle_fold_kernel)
 // Kernel headers, one per stage.  A kernel that is not a template is defined in the one unit that launches it.
 //   mppi_common.hpp    Dims, GenCtx, wave reductions
 //   mppi_lds.hpp       the dynamic-LDS layout of every kernel that carves one up: offsets for the kernel, the total for its launch site
@@ -226,6 +228,17 @@ struct MppiSolver {
         float weight = 1.0f;
         float lambda = 0.0f;           // what mppi_rollout_cost multiplies by: > 0, MPPI_LAMBDA_DEVICE, or 0 (none yet)
     } ac;
+
+    // risk-aware solves (capi_particles.hip): while P > 0 the rollout stage evaluates every sample from every particle into
+    // `costs` [P][N] and particle_fold_kernel folds the P costs of a sample into core.costs
+    struct Particles {
+        int P = 0;                     // start states set (0: off)
+        int mode = MPPI_RISK_MEAN;     // MPPI_RISK_*
+        int k = 1;                     // worst particles averaged under MPPI_RISK_CVAR (checked against P where the fold is launched)
+        DevBuf<float> table;           // [MPPI_MAX_PARTICLES][ds] (native models; allocated on first use)
+        DevBuf<float> costs;           // [P][N] of the last rollout (allocated on first use, grows on the set-up path)
+        bool costs_valid = false;      // ... and whether a rollout / mppi_set_particle_costs has filled it for the current P
+    } part;
 
     // temperature: statistics passes, the device-resident ESSPS / LBPS / Brent / MPO searches
     struct Search {
@@ -596,6 +609,10 @@ int flush_state_seq(mppi_handle_t h, hipStream_t s);
 // mapping, maps, model parameters): complete a pending state sequence with the settings of the solve it belongs to, on the
 // stream that solve ran on.
 inline int settle_state_seq(mppi_handle_t h) { return h->lazy.pending_out ? flush_state_seq(h, h->lazy.pending_stream) : MPPI_OK; }
+
+// capi_particles.hip: the rollout stage while particles are set (rollout from every particle, then the fold)
+int rollout_particles(mppi_handle_t h, hipStream_t s);
+int clone_particles(mppi_handle_t dst, mppi_handle_t src);
 
 // capi_search.hip
 int essps_prepare(mppi_handle_t h, double lam_min, double lam_max);

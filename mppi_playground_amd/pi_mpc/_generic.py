@@ -3,12 +3,30 @@
 softmax, reduction and warm start stay in the library."""
 from __future__ import annotations
 
+import contextlib
+import gc
 from typing import Dict
 
 import numpy as np
 import torch
 
 from pi_mpc._lazy import _ptr
+
+
+@contextlib.contextmanager
+def _no_collection_while_capturing():
+    """Around a stream capture: dead reference cycles that own HIP objects — an earlier solver with its captured graphs, their
+    memory pool and its library handle — must not be finalised INSIDE the capture (a destructor that calls into the runtime
+    there takes the process down; torch.cuda.graph no longer collects on entry).  Collect them before it and keep the cyclic
+    collector off until the capture has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class GenericPathMixin:
@@ -33,6 +51,35 @@ class GenericPathMixin:
             self._perturbed_action_seqs_buf = torch.empty(N, T, self._dim_control, device=self._device, dtype=self._dtype)
         U = self._perturbed_action_seqs_buf
         self._h.call("mppi_export_noise", None, _ptr(U), self._stream())
+        P = self._particles_P
+        if not P:
+            self._callable_pass(info)
+            self._h.call("mppi_set_costs", _ptr(self._generic_costs_keep), 1, self._stream())
+            return
+        # risk-aware solve: the two loops once per particle with the start state replaced (a captured graph reads the start
+        # state from the static buffer, so it is replayed once per particle), the [P, N] matrix goes to the library's fold —
+        # the same fold and the same meaning as on the native path
+        M = self.__dict__.get("_particle_matrix")
+        if M is None or M.shape[0] != P:
+            M = self._particle_matrix = torch.empty(P, N, device=self._device, dtype=self._dtype)
+        warm = self._graph_state == "warmup"
+        for m in range(P):
+            self._x0_tensor.copy_(self._particles_keep[m])
+            self._callable_pass(info, advance=False)
+            M[m].copy_(self._generic_costs_keep)
+        if warm and self._graph_state == "warmup":
+            self._graph_state = "capture"
+        # the particles decide costs only: `_state_seq_batch` (get_top_samples) and `state_seq` start from the nominal state
+        self._x0_tensor.copy_(x0)
+        S = self._state_seq_batch_buf
+        S[:, 0, :] = self._x0_tensor.repeat(N, 1)
+        for t in range(T):
+            S[:, t + 1, :] = self._dynamics(S[:, t, :], U[:, t, :])
+        self._h.call("mppi_set_particle_costs", _ptr(M), 1, self._stream())
+
+    def _callable_pass(self, info: Dict, advance: bool = True) -> None:
+        """One pass of the two loops from `_x0_tensor` -> `_generic_costs_keep`: eager, capturing, or a graph replay.
+        `advance`: an eager warm-up pass moves the solver on to the capture (the per-particle passes of one solve do that once)."""
         if self._graph_state == "replay":
             self._check_replay_info(info)
             self._graph.replay()
@@ -40,9 +87,8 @@ class GenericPathMixin:
             self._capture_callables(info)
         else:
             self._callable_loops(info)
-            if self._graph_state == "warmup":
+            if advance and self._graph_state == "warmup":
                 self._graph_state = "capture"  # the next solve captures (this one warmed the allocator / kernels up)
-        self._h.call("mppi_set_costs", _ptr(self._generic_costs_keep), 1, self._stream())
 
     def _callable_loops(self, info: Dict) -> None:
         """src/pi_mpc/mppi.py:280-336 on the static buffers: S <- rollout of U from x0, total costs -> _generic_costs_keep."""
@@ -82,7 +128,7 @@ class GenericPathMixin:
                 torch.cuda.current_stream(self._device).wait_stream(side)
                 torch.cuda.synchronize(self._device)
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=side):
+                with _no_collection_while_capturing(), torch.cuda.graph(g, stream=side):
                     self._b1_states = self._states_prediction(self._x0_tensor, self._b1_actions)
                 self._graph_b1 = g
             except Exception as e:  # noqa: BLE001  not capturable at batch 1: stay eager for this step
@@ -114,7 +160,7 @@ class GenericPathMixin:
             torch.cuda.synchronize(self._device)
             side = torch.cuda.Stream(device=self._device)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
+            with _no_collection_while_capturing(), torch.cuda.graph(g, stream=side):
                 self._callable_loops(info)
             self._graph = g
             self._graph_state = "replay"

@@ -337,3 +337,70 @@ def check_noise_beta_args(noise_beta, dim_control, noise_source="philox", action
         raise ValueError("noise_beta > 0 is not available with action_cost=True: the term's inverse covariance is diagonal in "
                          "time and would no longer be the KL term of the distribution sampled from")
     return b
+
+
+# ---- risk-aware solves (include/mppi_hip.h: mppi_set_particles)
+MAX_PARTICLES = 16                                # MPPI_MAX_PARTICLES
+RISK_MODES = {"mean": 0, "worst": 1, "cvar": 2}  # MPPI_RISK_*
+
+
+def check_risk_args(risk, risk_alpha):
+    """Validate the `risk` / `risk_alpha` keyword arguments of MPPI and return (risk, risk_alpha as a float).  ValueError for
+    an unknown measure and for risk_alpha outside (0, 1]."""
+    if risk not in RISK_MODES:
+        raise ValueError(f"risk must be 'mean', 'worst' or 'cvar', got {risk!r}")
+    a = float(risk_alpha)
+    if not (0.0 < a <= 1.0):
+        raise ValueError(f"risk_alpha must lie in (0, 1], got {risk_alpha}")
+    return risk, a
+
+
+def risk_k(risk_alpha, P):
+    """The number of worst particles CVaR averages: k = min(P, max(1, ceil(risk_alpha * P))), in float64."""
+    return int(min(int(P), max(1, math.ceil(float(risk_alpha) * int(P)))))
+
+
+def check_particles_shape(shape, dim_state):
+    """Validate the shape of a particle table [P, dim_state] (set_state_particles); returns P.  ValueError for a wrong shape,
+    P = 0 or P > 16."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 2 or shape[1] != int(dim_state):
+        raise ValueError(f"state particles: expected [P, {dim_state}], got {list(shape)}")
+    if not 1 <= shape[0] <= MAX_PARTICLES:
+        raise ValueError(f"state particles: P = {shape[0]}, need 1 <= P <= {MAX_PARTICLES} (None switches the feature off)")
+    return shape[0]
+
+
+def fold_particle_costs(matrix, mode, k=1):
+    """The fold of include/mppi_hip.h (particle_fold_kernel) restated in numpy, in the header's operation order: matrix [P, N]
+    fp32 -> [N] fp32.  `mode`: "mean" | "worst" | "cvar" (or MPPI_RISK_* 0 | 1 | 2); `k`: the worst particles averaged under
+    CVaR, 1 <= k <= P.  Every operation rounds on its own in fp32, the division is the IEEE quotient.  A NaN among the P costs
+    of a sample makes its folded cost NaN in every mode, as on the device."""
+    c = np.ascontiguousarray(matrix, dtype=F32)
+    if c.ndim != 2 or c.shape[0] < 1:
+        raise ValueError(f"particle costs: expected [P, N], got {list(c.shape)}")
+    P = c.shape[0]
+    mode = RISK_MODES.get(mode, mode)
+    if mode not in (0, 1, 2):
+        raise ValueError(f"unknown risk measure {mode!r}")
+    with np.errstate(invalid="ignore", over="ignore"):
+        if mode == 1:
+            a = c[0].copy()
+            for m in range(1, P):
+                a = np.maximum(a, c[m])
+        elif mode == 2:
+            k = int(k)
+            if not 1 <= k <= P:
+                raise ValueError(f"CVaR needs 1 <= k <= P, got k = {k}, P = {P}")
+            s = -np.sort(-c, axis=0)  # largest first (negation is exact; ties are interchangeable)
+            a = s[0].copy()
+            for j in range(1, k):
+                a = (a + s[j]).astype(F32)
+            a = (a / F32(k)).astype(F32)
+        else:
+            a = c[0].copy()
+            for m in range(1, P):
+                a = (a + c[m]).astype(F32)
+            a = (a / F32(P)).astype(F32)
+    a[np.isnan(c).any(axis=0)] = np.nan
+    return a.astype(F32)

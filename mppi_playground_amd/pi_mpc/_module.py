@@ -20,7 +20,7 @@ class ModuleProtocolMixin:
         """A second solver that continues EXACTLY like this one: same constructor arguments, a handle of its own, and every
         piece of dynamic state copied on the device (mppi_clone_state: warm start, noise identity, the last solve's costs,
         Savitzky-Golay history, the temperature and the device-resident search / dual state, model parameters, maps,
-        reference window and path index, options, the sigma table and settings of the covariance adaptation, the control-cost term's switch and weight, the noise correlation) or on the host (RNG stream position, the torch-CPU generator, temperatures
+        reference window and path index, options, the sigma table and settings of the covariance adaptation, the control-cost term's switch and weight, the noise correlation, the state particles with the risk measure and the last particle cost matrix) or on the host (RNG stream position, the torch-CPU generator, temperatures
         already fetched).  The callables are deep-copied like the reference's attributes would be — with them the environment
         / controller objects that own the model's parameters — and the native tags re-resolved on the copies."""
         if self._world > 1 or self._force_exchange:
@@ -48,11 +48,11 @@ class ModuleProtocolMixin:
         # host-side dynamic state
         for k in ("_solve_idx", "_lambda_value", "_last_lambda_value", "_lambda_override", "_used_known", "_essps_prev",
                   "_params_set", "_fused_error_seen", "_auto_params_sent", "_lbps_delta", "_essps_target_ess", "_lambda_min",
-                  "_lambda_max"):
+                  "_lambda_max", "_risk", "_risk_alpha", "_particles_P"):
             it[k] = me[k]
         it["_lambda_pending"], it["_lambda_stream"] = False, None
         for k in ("_previous_action_seq", "_action_out", "_state_out", "_stats", "_summary", "_mean_of_last_solve", "_injected",
-                  "_x0_tensor"):
+                  "_x0_tensor", "_particles_keep"):
             v = me.get(k)
             it[k] = v.detach().clone() if torch.is_tensor(v) else v
         if me.get("_previous_action_seq") is me.get("_action_out"):  # (the reference keeps ONE tensor for both, mppi.py:452,460)
@@ -84,7 +84,7 @@ class ModuleProtocolMixin:
     def get_extra_state(self) -> Dict[str, Any]:
         """The solver's dynamic state for state_dict() (entry `_extra_state`; the reference keeps the same things as plain
         attributes, which its state_dict() silently drops): warm start, Savitzky-Golay history, RNG stream position (Philox
-        solve index and the torch-CPU generator), the adapted sigma table (adapt_covariance), the noise correlation (`noise_beta`), the temperature and — MPO — the dual with its Adam moments."""
+        solve index and the torch-CPU generator), the adapted sigma table (adapt_covariance), the noise correlation (`noise_beta`), the risk measure and the state particles, the temperature and — MPO — the dual with its Adam moments."""
         if self._lambda_pending:
             self._fetch_lambda()
         mean = torch.empty(self._horizon, self._dim_control, device=self._device, dtype=self._dtype)
@@ -96,6 +96,8 @@ class ModuleProtocolMixin:
         if self._adapt_covariance:  # the adapted per-step standard deviations
             out["sigma_seq"] = self.sigma_seq.cpu()
         out["noise_beta"] = self.noise_beta
+        parts = self.state_particles  # risk-aware solves: the measure, and the particle table while one is set
+        out["risk"], out["risk_alpha"], out["particles"] = self._risk, self._risk_alpha, None if parts is None else parts.cpu()
         if self._auto_lambda == "MPO":
             if self._rule_on_device == "MPO":
                 st4 = (C.c_double * 4)()
@@ -127,6 +129,9 @@ class ModuleProtocolMixin:
             torch.cuda.current_stream(self._device).synchronize()
         if state.get("noise_beta") is not None:  # (absent in a state written before the setting existed: it stays as constructed)
             self.set_noise_beta(state["noise_beta"])
+        if state.get("risk") is not None:  # (absent in a state written before the setting existed: it stays as constructed)
+            self.set_risk(state["risk"], state.get("risk_alpha"))
+            self.set_state_particles(state.get("particles"))
         if state.get("cpu_generator") is not None and self._cpu_gen is not None:
             self._cpu_gen.set_state(state["cpu_generator"])
         if state.get("mpo") is not None and self._auto_lambda == "MPO":

@@ -94,6 +94,8 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         action_cost: bool = False,
         action_cost_weight: float = 1.0,
         noise_beta=0.0,
+        risk: str = "mean",
+        risk_alpha: float = 1.0,
         _force_exchange: bool = False,
     ) -> None:
         """Arguments up to `seed` are the reference's (src/pi_mpc/mppi.py:24-47).
@@ -185,6 +187,19 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                 adapt_covariance, every temperature rule and shard_samples=True.  Not with noise_source="torch_cpu" (the
                 filter would need a second implementation on the host) or action_cost=True (the term's inverse covariance
                 is diagonal in time): ValueError, as for a value outside [0, 1) or of the wrong length.
+            risk, risk_alpha: the risk measure of a RISK-AWARE solve, used only while a set of start states is set with
+                set_state_particles() (default: none set — every solve is the plain one, bit for bit, and nothing else is
+                launched).  With P particles every sample is rolled out from every particle and its P costs are folded into one:
+                "mean" (default), "worst" (the maximum) or "cvar" — the mean of the k worst, k = min(P, max(1, ceil(risk_alpha *
+                P))) (risk_alpha in (0, 1]: 1 is the descending-order mean, 1 / P the worst case).  `_costs`, the temperature
+                rules, the weights, get_top_samples and adapt_covariance see the folded cost; `particle_costs` is the [P, N]
+                matrix.  forward(state) is unchanged: `state` stays the nominal estimate, `state_seq` and every re-roll start
+                from it — the particles decide costs only.  Small problems take the multi-kernel sequence while particles are
+                set.  set_risk() changes the measure between solves, reset() keeps it and drops the particles, deepcopy and
+                state_dict() carry both.  Opaque callables run their two loops once per particle (with graph_callables the
+                captured graph is replayed once per particle: it reads the start state from a static buffer) and one more
+                dynamics-only pass from the nominal state for `_state_seq_batch`.  ValueError for an unknown measure or
+                risk_alpha outside (0, 1].
             shard_samples: treat `num_samples` as the GLOBAL sample count and let this rank own the
                 contiguous block rank*N/W .. (rank+1)*N/W of it (torch.distributed must be
                 initialised); the 4+T*dc-float shard summaries are exchanged once per solve with one RCCL
@@ -208,7 +223,7 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                           graph_callables=graph_callables, lazy_state_seq=lazy_state_seq, adapt_covariance=adapt_covariance,
                           cov_rate=cov_rate, cov_floor=cov_floor, sigma_min=sigma_min, sigma_max=sigma_max,
                           action_cost=action_cost, action_cost_weight=action_cost_weight, noise_beta=noise_beta,
-                          _force_exchange=_force_exchange)
+                          risk=risk, risk_alpha=risk_alpha, _force_exchange=_force_exchange)
         assert u_min.shape == (dim_control,)
         assert u_max.shape == (dim_control,)
         assert sigmas.shape == (dim_control,)
@@ -221,6 +236,9 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         self._action_cost_weight = _host.check_action_cost_args(action_cost, action_cost_weight, sigmas, adapt_covariance,
                                                                 cov_floor, sigma_min)
         self._noise_beta = _host.check_noise_beta_args(noise_beta, dim_control, noise_source, action_cost)
+        self._risk, self._risk_alpha = _host.check_risk_args(risk, risk_alpha)
+        self._particles_P = 0        # start states set with set_state_particles (0: none — the plain solve)
+        self._particles_keep = None  # the table as it was handed over (alive until the copy ran; the generic path reads it)
         dev = torch.device(device)
         if dev.type != "cuda":
             raise ValueError(f"device={dev}: this MPPI runs its hot path on MI355X only; there is no CPU path "
@@ -381,6 +399,8 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             self._h.call("mppi_set_action_cost", 1, self._action_cost_weight)
         if self._noise_beta.any():  # (all zero: the default draw, no call into the library)
             self._h.call("mppi_set_noise_correlation", self._noise_beta.ctypes.data_as(C.c_void_p))
+        if self._risk != "mean":  # (the default measure: no call into the library)
+            self._h.call("mppi_set_risk", _host.RISK_MODES[self._risk], 1)
         # the LBPS search and the MPO step run inside the library (no interpreter work per probe) whenever the
         # statistics come from this device alone; sharded solvers combine the shards' statistics in Python
         self._search_in_library = auto_lambda_stats == "device" and self._world == 1
@@ -735,6 +755,71 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         if self._adapt_covariance:  # the adapted table goes back to the constructor's `sigmas`
             self._sigma_seq_reset = self._sigmas.repeat(self._horizon, 1).contiguous()  # (alive until the copy ran)
             self._h.call("mppi_set_sigma_table", _ptr(self._sigma_seq_reset), 1, self._stream())
+        self.set_state_particles(None)  # (the risk measure stays)
+
+    # ------------------------------------------------------------------ risk-aware solves
+    def set_state_particles(self, particles) -> None:
+        """The set of start states the next solves score every sample from: a [P, dim_state] tensor (device or host) or array,
+        1 <= P <= 16 — a filter's particles, draws round an estimate; call it every tick.  None switches the feature off (the
+        next solve is the plain one).  On the current stream, no host wait: a tensor on the solver's device is copied there,
+        anything else goes through the pinned staging ring.  ValueError for a wrong shape or P > 16 (before the handle is
+        touched).  Works with every noise source (the torch-CPU draw is injected as tiles, which the particle rollout reads)."""
+        if particles is None:
+            if self._particles_P:
+                self._h.call("mppi_set_particles", None, 0, 0, self._stream())
+            self._particles_P, self._particles_keep = 0, None
+            return
+        P = _host.check_particles_shape(particles.shape, self._dim_state)
+        st = self._stream()
+        on_device = torch.is_tensor(particles) and particles.is_cuda and particles.device == self._device
+        if on_device or self._model is None:  # (the generic path replaces the callables' start state on the device)
+            dev = torch.as_tensor(particles).detach().to(self._device, self._dtype).contiguous()
+            self._h.call("mppi_set_particles", _ptr(dev), P, 1, st)
+            self._particles_keep = dev  # (alive until the next table: the copy reads it in stream order)
+        else:
+            host = np.ascontiguousarray(particles.detach().cpu().numpy() if torch.is_tensor(particles) else particles,
+                                        dtype=np.float32)
+            if not np.all(np.isfinite(host)):
+                raise ValueError("state particles: every value must be finite")
+            self._h.call("mppi_set_particles", host.ctypes.data_as(C.c_void_p), P, 0, st)
+            self._particles_keep = None
+        self._particles_P = P
+        self._push_risk()
+
+    def _push_risk(self) -> None:
+        k = _host.risk_k(self._risk_alpha, self._particles_P) if self._particles_P else 1
+        self._h.call("mppi_set_risk", _host.RISK_MODES[self._risk], k)
+
+    def set_risk(self, risk: str, risk_alpha: Optional[float] = None) -> None:
+        """Change the risk measure between solves (same values and errors as the constructor arguments; risk_alpha None keeps
+        the current one).  deepcopy and state_dict() carry it."""
+        self._risk, self._risk_alpha = _host.check_risk_args(risk, self._risk_alpha if risk_alpha is None else risk_alpha)
+        self._ctor["risk"], self._ctor["risk_alpha"] = self._risk, self._risk_alpha
+        self._push_risk()
+
+    @property
+    def risk(self) -> Tuple[str, float]:
+        """(risk measure, risk_alpha) as set."""
+        return self._risk, self._risk_alpha
+
+    @property
+    def state_particles(self) -> Optional[torch.Tensor]:
+        """The particle table the library holds, [P, dim_state] on the device (a copy), or None while none is set."""
+        if not self._particles_P:
+            return None
+        if self._model is None:  # (a generic handle records the count only: the table lives here)
+            return self._particles_keep.clone()
+        out = torch.empty(self._particles_P, self._dim_state, device=self._device, dtype=self._dtype)
+        self._h.call("mppi_get_particles", _ptr(out), None, 1, self._stream())
+        return out
+
+    @property
+    def particle_costs(self) -> torch.Tensor:
+        """The [P, N] cost matrix of the last solve (row m: the costs of every sample from particle m, before the fold and
+        before the control-cost term), on the device (a copy).  MppiError while no particles are set."""
+        out = torch.empty(max(self._particles_P, 1), self._local_samples, device=self._device, dtype=self._dtype)
+        self._h.call("mppi_get_particle_costs", _ptr(out), 1, self._stream())
+        return out
 
     @property
     def noise_beta(self) -> torch.Tensor:
