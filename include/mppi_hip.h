@@ -570,6 +570,13 @@ int mppi_essps_lambda(mppi_handle_t h, double target_ess, double lam_min, double
  * (synchronises the stream).  Identical arithmetic to mppi_essps_lambda (both call csrc/host_search.hpp). */
 #define MPPI_LAMBDA_DEVICE (-1.0f)
 int mppi_essps_lambda_device(mppi_handle_t h, double target_ess, double lam_min, double lam_max, void* stream);
+/* What the device-resident ESSPS search carries from one solve to the next (the first grid its last search left for the next
+ * one, built around that search's root), as an opaque blob: for callers that save a solver and restore it in another process
+ * (mppi_clone_state copies the same state between two handles).  mppi_essps_get_state: *bytes_out_host = the blob's size, 0
+ * while no search has run; out_host NULL asks for the size only.  mppi_essps_set_state: a handle restored from the blob
+ * searches on bit for bit like the one it was read from.  A blob of another size is refused.  Both synchronise the device. */
+int mppi_essps_get_state(mppi_handle_t h, void* out_host, int64_t* bytes_out_host);
+int mppi_essps_set_state(mppi_handle_t h, const void* in_host, int64_t bytes);
 /* Passes over the costs the last device-resident search took (ESSPS: 1 or 2; LBPS: 2); 0 = none yet.  Synchronises. */
 int mppi_search_passes(mppi_handle_t h, void* stream);
 /* The temperature a device-resident rule left in HBM, and (lambda_used_out_host != NULL) the one the last solve's weights

@@ -50,6 +50,7 @@ SYMBOLS = [
     "mppi_set_discs", "mppi_get_discs", "mppi_set_disc_softness", "mppi_get_disc_softness",
     "mppi_set_particles", "mppi_get_particles", "mppi_set_risk", "mppi_get_risk", "mppi_get_particle_costs",
     "mppi_set_particle_costs",
+    "mppi_essps_get_state", "mppi_essps_set_state",
 ]
 
 
@@ -182,6 +183,8 @@ def load():
     lib.mppi_get_risk.argtypes = [vp, vp, vp]
     lib.mppi_get_particle_costs.argtypes = [vp, vp, i32, vp]
     lib.mppi_set_particle_costs.argtypes = [vp, vp, i32, vp]
+    lib.mppi_essps_get_state.argtypes = [vp, vp, vp]
+    lib.mppi_essps_set_state.argtypes = [vp, vp, i64]
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the .so does not export what the header declares
         if name not in ("mppi_version", "mppi_last_error"):

@@ -284,6 +284,39 @@ int mppi_essps_lambda_device(mppi_handle_t h, double target_ess, double lam_min,
     return MPPI_OK;
 }
 
+// The state the device-resident ESSPS search carries from one solve to the next, as an opaque blob for callers that save a
+// solver and restore it elsewhere (mppi_clone_state copies the same buffers between two handles): {lam_min, lam_max} the first
+// grid was built for, EsspsDev (the first grid of the NEXT search and its logs, left behind by the last one) and the three
+// fp32 grids.  A search restored from it continues bit for bit.  Set-up path: both synchronise the device.
+static constexpr size_t ESSPS_STATE_BYTES = 2 * sizeof(double) + sizeof(EsspsDev) + sizeof(float) * 3 * STATS_L;
+int mppi_essps_get_state(mppi_handle_t h, void* out_host, int64_t* bytes_out_host) {
+    if (!h || !bytes_out_host) return fail(h, MPPI_E_INVALID, "null");
+    const bool any = h->search.essps_lo > 0.0;  // (no search has run on this handle yet: nothing to carry)
+    *bytes_out_host = any ? (int64_t)ESSPS_STATE_BYTES : 0;
+    if (!out_host || !any) return MPPI_OK;
+    char* o = (char*)out_host;
+    const double range[2] = {h->search.essps_lo, h->search.essps_hi};
+    HIP_TRY(h, hipDeviceSynchronize());
+    memcpy(o, range, sizeof(range));
+    HIP_TRY(h, hipMemcpy(o + sizeof(range), h->search.essps_dev, sizeof(EsspsDev), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(o + sizeof(range) + sizeof(EsspsDev), h->search.lams_dev, sizeof(float) * 3 * STATS_L, hipMemcpyDeviceToHost));
+    return MPPI_OK;
+}
+
+int mppi_essps_set_state(mppi_handle_t h, const void* in_host, int64_t bytes) {
+    if (!h || !in_host) return fail(h, MPPI_E_INVALID, "null");
+    if (bytes != (int64_t)ESSPS_STATE_BYTES) return fail(h, MPPI_E_INVALID, "essps state: a blob of another size (another build wrote it)");
+    const char* in = (const char*)in_host;
+    double range[2];
+    memcpy(range, in, sizeof(range));
+    if (int rc = check_essps(h, true, 1.0, range[0], range[1])) return rc;
+    if (int rc = essps_prepare(h, range[0], range[1])) return rc;  // (the range and its logs; the cold grid is overwritten below)
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemcpy(h->search.essps_dev, in + sizeof(range), sizeof(EsspsDev), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->search.lams_dev, in + sizeof(range) + sizeof(EsspsDev), sizeof(float) * 3 * STATS_L, hipMemcpyHostToDevice));
+    return MPPI_OK;
+}
+
 // The temperature a device-resident rule left behind (and, optionally, the one the last solve's weights used: the same
 // for ESSPS / LBPS, the previous one for MPO).  Synchronises the stream.
 int mppi_get_lambda(mppi_handle_t h, double* lambda_out_host, double* lambda_used_out_host, void* stream) {

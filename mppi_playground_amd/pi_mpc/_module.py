@@ -84,7 +84,7 @@ class ModuleProtocolMixin:
     def get_extra_state(self) -> Dict[str, Any]:
         """The solver's dynamic state for state_dict() (entry `_extra_state`; the reference keeps the same things as plain
         attributes, which its state_dict() silently drops): warm start, Savitzky-Golay history, RNG stream position (Philox
-        solve index and the torch-CPU generator), the adapted sigma table (adapt_covariance), the noise correlation (`noise_beta`), the risk measure and the state particles, the temperature and — MPO — the dual with its Adam moments."""
+        solve index and the torch-CPU generator), the adapted sigma table (adapt_covariance), the noise correlation (`noise_beta`), the risk measure and the state particles, the temperature, the warm start of the device-resident ESSPS search and — MPO — the dual with its Adam moments."""
         if self._lambda_pending:
             self._fetch_lambda()
         mean = torch.empty(self._horizon, self._dim_control, device=self._device, dtype=self._dtype)
@@ -98,6 +98,13 @@ class ModuleProtocolMixin:
         out["noise_beta"] = self.noise_beta
         parts = self.state_particles  # risk-aware solves: the measure, and the particle table while one is set
         out["risk"], out["risk_alpha"], out["particles"] = self._risk, self._risk_alpha, None if parts is None else parts.cpu()
+        if self._rule_on_device == "ESSPS":  # the warm start of the device-resident search: the grid its last search left behind
+            n = C.c_int64(0)
+            self._h.call("mppi_essps_get_state", None, C.byref(n))
+            if n.value:
+                blob = (C.c_char * n.value)()
+                self._h.call("mppi_essps_get_state", blob, C.byref(n))
+                out["essps"] = bytes(blob)
         if self._auto_lambda == "MPO":
             if self._rule_on_device == "MPO":
                 st4 = (C.c_double * 4)()
@@ -147,6 +154,15 @@ class ModuleProtocolMixin:
             self._lambda_value = state["lambda"]
             if self._rule_on_device == "MPO":
                 self._lambda_override = None
+            elif self._rule_on_device in ("ESSPS", "LBPS") and isinstance(state["lambda"], float) and state["lambda"] > 0.0:
+                # The temperature the saved solver's last search left ON THE DEVICE: the control-cost term of the next solve
+                # is scaled with it (it is read when the rollout starts, before this solve's search), and a fresh handle
+                # holds none — the term would get a zero factor for one solve.  mppi_mpo_reset puts a temperature there
+                # (the dual it also restarts is not used under these rules).
+                self._h.call("mppi_mpo_reset", float(state["lambda"]), 0.1, 0.2)
+        if state.get("essps") is not None and self._rule_on_device == "ESSPS":  # (after the temperature: the search continues warm)
+            blob = state["essps"]
+            self._h.call("mppi_essps_set_state", C.c_char_p(blob), len(blob))
         self._last_lambda_value = state.get("last_lambda")
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
