@@ -198,6 +198,29 @@ int mppi_set_reference(mppi_handle_t h, const float* ref_host, int rows, void* s
  * take these models (MPPI_E_INVALID: it has no handle to take the table from). */
 int mppi_set_mlp(mppi_handle_t h, const float* table_host, int n_floats, int hidden_layers, int activation, int residual,
                  void* stream);
+/* Model ensembles for the learned dynamics: E = n_members networks of ONE architecture (one set of flags), each a table as
+ * mppi_set_mlp takes it, laid out tables_host[E][n_floats] and kept in one device buffer, 1 <= E <= MPPI_MAX_PARTICLES.
+ * mppi_set_mlp is the case E = 1.  A risk-aware solve (mppi_set_particles) may then carry every particle through a member of
+ * its own (mppi_set_particle_members): the cost of (sample i, particle m) is what a plain handle holding member members[m]'s
+ * table computes for sample i from x0 = particles[m] — the arithmetic of mppi_set_mlp, the same functor, read from that
+ * member's table — and the fold judges a plan by the mean, the worst case or the CVaR over the members.
+ * THE NOMINAL MEMBER: everything outside the particle rollout evaluates ONE network, member `nominal` — the rollout of a
+ * plain solve, mppi_finalize's state sequence (a lazily completed one included), the re-rolls of mppi_top_samples /
+ * mppi_rollout_samples / mppi_rollout_candidates and mppi_rollout_actions.  The members decide particle costs only.
+ *   mppi_set_mlp_ensemble  checks as mppi_set_mlp does (count, flags, finite values; 0 <= nominal < E), completes a pending
+ *                        lazily completed state sequence with the OLD weights first, stages and copies the E tables on
+ *                        `stream`.  A buffer too small for them is reallocated (blocking: set-up path).
+ *   mppi_set_mlp_member  replaces member e's table (a model learned online: one member per tick); the flags stay.  A pending
+ *                        state sequence is completed with the old weights first.  MPPI_E_STATE before any table was set.
+ *   mppi_set_mlp_nominal re-points the nominal member (a pending state sequence is completed under the OLD one first).
+ *   mppi_get_mlp_ensemble  E and the nominal index (either pointer may be NULL); E = 0 while no table is set.
+ * MPPI_E_INVALID for another model's handle, E = 0 or E > MPPI_MAX_PARTICLES, an index out of range, a wrong count, a flag out
+ * of range or a value that is not finite.  mppi_clone_state copies all E tables, the flags and the nominal index. */
+int mppi_set_mlp_ensemble(mppi_handle_t h, const float* tables_host /* [n_members][n_floats] */, int n_members, int n_floats,
+                          int hidden_layers, int activation, int residual, int nominal, void* stream);
+int mppi_set_mlp_member(mppi_handle_t h, int e, const float* table_host, int n_floats, void* stream);
+int mppi_set_mlp_nominal(mppi_handle_t h, int e);
+int mppi_get_mlp_ensemble(mppi_handle_t h, int* n_members_out, int* nominal_out);
 /* Moving obstacles for MPPI_MODEL_NAV2D_DISCS (dynamics, parameters and maps of MPPI_MODEL_NAV2D): the predicted discs as a
  * table with one row per horizon step, discs [rows][n][4] = {cx, cy, r2, w}: centre, SQUARED radius (formed by the caller)
  * and penalty of disc j at step t; rows >= T, 0 <= n <= MPPI_MAX_DISCS.  Stage cost of step t, on the state (x, y, .) the
@@ -495,6 +518,19 @@ int mppi_set_risk(mppi_handle_t h, int mode, int k);
 int mppi_get_risk(mppi_handle_t h, int* mode_out, int* k_out);
 int mppi_get_particle_costs(mppi_handle_t h, float* out /* [P][N] */, int on_device, void* stream);
 int mppi_set_particle_costs(mppi_handle_t h, const float* src /* [P][N] */, int on_device, void* stream);
+/* The map from particle to ensemble member (MPPI_MODEL_MLP41 / MLP42 with mppi_set_mlp_ensemble): members[P], particle m is
+ * rolled out through member members[m]; NULL or P = 0: no map (every particle through the nominal member — the launch is
+ * exactly the one without this feature).  Either this call or mppi_set_particles may come first: the rollout checks, before
+ * anything is launched, that the map's length is the particle count and that every entry is < E (else MPPI_E_INVALID).
+ * Switching the particles off (mppi_set_particles with P = 0) drops the map.  MPPI_E_INVALID for a map on a handle of another
+ * model, P > MPPI_MAX_PARTICLES or a negative entry.  The block of particle m reads its entry — the member's offset into the
+ * table buffer, staged on the device in stream order by the rollout that first uses the map — at a block-uniform address and
+ * moves its copy of the table pointer: the weights still arrive as scalar operands.  Everything behind the rollout (the fold,
+ * the minimum key, the control-cost term behind the fold, the temperature rules, sharding, both noise paths) is what it is
+ * for particles.  Sharded handles: every rank must be given the same map.  mppi_clone_state copies it.
+ *   mppi_get_particle_members  the map (out may be NULL to query its length only; 0: none). */
+int mppi_set_particle_members(mppi_handle_t h, const int* members /* [P] */, int P);
+int mppi_get_particle_members(mppi_handle_t h, int* out /* [P] */, int* P_out);
 /* Lazily completed state sequences (mppi_set_option("lazy_state_seq", 1)).  The reference returns `state_seq` — the batch-1
  * rollout of the solution, mppi.py:448-449,508-524 — with the action sequence, but nothing on a control loop's critical
  * path needs it: the next solve samples around the mean, env.step applies a[0].  With the option set, mppi_finalize /

@@ -50,6 +50,8 @@ SYMBOLS = [
     "mppi_set_discs", "mppi_get_discs", "mppi_set_disc_softness", "mppi_get_disc_softness",
     "mppi_set_particles", "mppi_get_particles", "mppi_set_risk", "mppi_get_risk", "mppi_get_particle_costs",
     "mppi_set_particle_costs",
+    "mppi_set_mlp_ensemble", "mppi_set_mlp_member", "mppi_set_mlp_nominal", "mppi_get_mlp_ensemble",
+    "mppi_set_particle_members", "mppi_get_particle_members",
     "mppi_essps_get_state", "mppi_essps_set_state",
 ]
 
@@ -183,6 +185,12 @@ def load():
     lib.mppi_get_risk.argtypes = [vp, vp, vp]
     lib.mppi_get_particle_costs.argtypes = [vp, vp, i32, vp]
     lib.mppi_set_particle_costs.argtypes = [vp, vp, i32, vp]
+    lib.mppi_set_mlp_ensemble.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.mppi_set_mlp_member.argtypes = [vp, i32, vp, i32, vp]
+    lib.mppi_set_mlp_nominal.argtypes = [vp, i32]
+    lib.mppi_get_mlp_ensemble.argtypes = [vp, vp, vp]
+    lib.mppi_set_particle_members.argtypes = [vp, vp, i32]
+    lib.mppi_get_particle_members.argtypes = [vp, vp, vp]
     lib.mppi_essps_get_state.argtypes = [vp, vp, vp]
     lib.mppi_essps_set_state.argtypes = [vp, vp, i64]
     for name in SYMBOLS:

@@ -341,10 +341,11 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
         publish_step_table(dst);
     }
     dm.soft_reach = sm.soft_reach; dm.soft_skirt = sm.soft_skirt;  // (the coefficients they stand for were copied with ctx)
-    if (sm.mlp && sm.ctx.ref) {  // learned dynamics: the weight table, with the flags that ride in ref_rows
+    if (sm.mlp && sm.ctx.ref) {  // learned dynamics: every member's weight table, the nominal index, the flags that ride in ref_rows
         if (dm.mlp.n != sm.mlp.n) HIP_TRY(dst, dm.mlp.alloc(sm.mlp.n));
         CLONE(model.mlp);
-        dm.ctx.ref = dm.mlp; dm.ctx.ref_rows = sm.ctx.ref_rows;
+        dm.mlp_members = sm.mlp_members; dm.mlp_nominal = sm.mlp_nominal;
+        dm.ctx.ref = dm.mlp.p + (sm.ctx.ref - sm.mlp.p); dm.ctx.ref_rows = sm.ctx.ref_rows;
     }
     if (sm.center_n) {
         HIP_TRY(dst, dm.center8.alloc(sm.center8.n));

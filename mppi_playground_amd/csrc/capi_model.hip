@@ -273,6 +273,80 @@ int mppi_set_mlp(mppi_handle_t h, const float* table, int n_floats, int hidden_l
     h->model.ctx.ref = h->model.mlp;
     h->model.ctx.ref_rows = (hidden_layers == 2 ? MLP_TWO_LAYERS : 0) | (activation == MPPI_MLP_TANH ? MLP_TANH : 0) |
                             (residual ? MLP_RESIDUAL : 0);
+    h->model.mlp_members = 1; h->model.mlp_nominal = 0;  // (an ensemble of one, in the front of whatever the buffer holds)
+    return MPPI_OK;
+}
+
+// one member's table through the staging ring into its place in the buffer, in stream order
+static int upload_mlp_member(mppi_handle_t h, int e, const float* table, int n_floats, hipStream_t s) {
+    float* st = nullptr; hipEvent_t ev = nullptr;
+    if (int rc = stage_slot(h, (size_t)n_floats, &st, &ev)) return rc;
+    std::memcpy(st, table, sizeof(float) * (size_t)n_floats);
+    HIP_TRY(h, hipMemcpyAsync(h->model.mlp.p + (size_t)e * (size_t)n_floats, st, sizeof(float) * (size_t)n_floats, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(ev, s));
+    return MPPI_OK;
+}
+
+int mppi_set_mlp_ensemble(mppi_handle_t h, const float* tables, int n_members, int n_floats, int hidden_layers, int activation,
+                          int residual, int nominal, void* stream) {
+    if (!h || !tables) return fail(h, MPPI_E_INVALID, "bad weight tables");
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the weight tables belong to the learned-dynamics models");
+    if (n_members < 1 || n_members > MPPI_MAX_PARTICLES)
+        return fail(h, MPPI_E_INVALID, "weight tables: 1 <= n_members <= MPPI_MAX_PARTICLES (16)");
+    if (nominal < 0 || nominal >= n_members) return fail(h, MPPI_E_INVALID, "weight tables: the nominal member is one of the n_members");
+    if (n_floats != mlp_table_floats(h->dc)) return fail(h, MPPI_E_INVALID, "weight table: wrong number of values for this model");
+    if (hidden_layers < 1 || hidden_layers > 2 || (activation != MPPI_MLP_RELU && activation != MPPI_MLP_TANH) ||
+        (residual != 0 && residual != 1))
+        return fail(h, MPPI_E_INVALID, "weight table: hidden_layers 1 or 2, activation relu or tanh, residual 0 or 1");
+    const size_t total = (size_t)n_members * (size_t)n_floats;
+    for (size_t i = 0; i < total; ++i)
+        if (!std::isfinite(tables[i])) return fail(h, MPPI_E_INVALID, "weight table: every value must be finite");
+    if (int rc = settle_state_seq(h)) return rc;  // a lazily completed state sequence belongs to the OLD weights: roll it out first
+    hipStream_t s = (hipStream_t)stream;
+    if (h->model.mlp.n < total) {  // (blocking: earlier launches may still read the old buffer)
+        HIP_TRY(h, hipDeviceSynchronize());
+        h->model.ctx.ref = nullptr; h->model.mlp_members = 0;
+        HIP_TRY(h, h->model.mlp.alloc(total));
+    }
+    for (int e = 0; e < n_members; ++e)
+        if (int rc = upload_mlp_member(h, e, tables + (size_t)e * (size_t)n_floats, n_floats, s)) return rc;
+    h->model.mlp_members = n_members; h->model.mlp_nominal = nominal;
+    h->model.ctx.ref = h->model.mlp.p + (size_t)nominal * (size_t)n_floats;
+    h->model.ctx.ref_rows = (hidden_layers == 2 ? MLP_TWO_LAYERS : 0) | (activation == MPPI_MLP_TANH ? MLP_TANH : 0) |
+                            (residual ? MLP_RESIDUAL : 0);
+    return MPPI_OK;
+}
+
+int mppi_set_mlp_member(mppi_handle_t h, int e, const float* table, int n_floats, void* stream) {
+    if (!h || !table) return fail(h, MPPI_E_INVALID, "bad weight table");
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the weight table belongs to the learned-dynamics models");
+    if (!h->model.ctx.ref || h->model.mlp_members < 1)
+        return fail(h, MPPI_E_STATE, "no weight table: call mppi_set_mlp or mppi_set_mlp_ensemble first");
+    if (e < 0 || e >= h->model.mlp_members) return fail(h, MPPI_E_INVALID, "weight table: no such member");
+    if (n_floats != mlp_table_floats(h->dc)) return fail(h, MPPI_E_INVALID, "weight table: wrong number of values for this model");
+    for (int i = 0; i < n_floats; ++i)
+        if (!std::isfinite(table[i])) return fail(h, MPPI_E_INVALID, "weight table: every value must be finite");
+    if (int rc = settle_state_seq(h)) return rc;  // a lazily completed state sequence belongs to the OLD weights: roll it out first
+    return upload_mlp_member(h, e, table, n_floats, (hipStream_t)stream);
+}
+
+int mppi_set_mlp_nominal(mppi_handle_t h, int e) {
+    if (!h) return MPPI_E_INVALID;
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the nominal member belongs to the learned-dynamics models");
+    if (!h->model.ctx.ref || h->model.mlp_members < 1)
+        return fail(h, MPPI_E_STATE, "no weight table: call mppi_set_mlp or mppi_set_mlp_ensemble first");
+    if (e < 0 || e >= h->model.mlp_members) return fail(h, MPPI_E_INVALID, "nominal member: no such member");
+    if (int rc = settle_state_seq(h)) return rc;  // a lazily completed state sequence belongs to the OLD nominal member
+    h->model.mlp_nominal = e;
+    h->model.ctx.ref = h->model.mlp.p + (size_t)e * (size_t)mlp_table_floats(h->dc);
+    return MPPI_OK;
+}
+
+int mppi_get_mlp_ensemble(mppi_handle_t h, int* n_members_out, int* nominal_out) {
+    if (!h) return MPPI_E_INVALID;
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the weight tables belong to the learned-dynamics models");
+    if (n_members_out) *n_members_out = h->model.ctx.ref ? h->model.mlp_members : 0;
+    if (nominal_out) *nominal_out = h->model.mlp_nominal;
     return MPPI_OK;
 }
 

@@ -1,6 +1,8 @@
 // capi_particles.hip — C ABI (include/mppi_hip.h): risk-aware solves.  The table of start states ("particles"), the risk
 // measure, the rollout stage while particles are set (rollout_particles_kernel from every particle, then particle_fold_kernel)
-// and the [P][N] cost matrix's get / set.  The kernels are in mppi_particles.hpp; this unit is the only one that launches them.
+// and the [P][N] cost matrix's get / set, and the map from particle to ensemble member of the learned-dynamics models
+// (mppi_set_particle_members).  The kernels are in mppi_particles.hpp; this unit is the only one that launches them.
+#include <algorithm>
 #include <cmath>
 
 #include "mppi_handle.hpp"
@@ -46,8 +48,33 @@ int rollout_particles(mppi_handle_t h, hipStream_t s) {
     if (h->opt.mapping == 1) return fail(h, MPPI_E_INVALID, "particles are not available with mapping = 1");
     if (p.mode == MPPI_RISK_CVAR && (p.k < 1 || p.k > p.P))  // (before anything is launched)
         return fail(h, MPPI_E_INVALID, "risk measure: CVAR needs 1 <= k <= P (mppi_set_risk / mppi_set_particles)");
+    // the map from particle to ensemble member (before anything is launched): its length is the particle count, every entry a member
+    ModelCtx ctx = h->model.ctx;
+    if (!p.members.empty()) {
+        if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "particle members belong to the learned-dynamics models");
+        if ((int)p.members.size() != p.P)
+            return fail(h, MPPI_E_INVALID, "particle members: the map's length is not the particle count (mppi_set_particle_members / mppi_set_particles)");
+        for (int e : p.members)
+            if (e >= h->model.mlp_members)
+                return fail(h, MPPI_E_INVALID, "particle members: an entry is not a member of the ensemble (mppi_set_mlp_ensemble)");
+    }
     if (int rc = flush_state_seq(h, s)) return rc;  // (the particle launch does not carry the rider block)
     if (int rc = reserve_particle_costs(h, p.P)) return rc;
+    if (!p.members.empty()) {  // the members' offsets into the weight buffer, staged in stream order; the launch's ctx starts at member 0
+        if (!p.member_off) HIP_TRY(h, p.member_off.alloc_set(MPPI_MAX_PARTICLES, 0));
+        if (!p.member_off_valid) {
+            float bits[MPPI_MAX_PARTICLES] = {};  // (the int32 offsets, as the staging ring carries them)
+            for (int m = 0; m < p.P; ++m) {
+                const int32_t off = p.members[(size_t)m] * mlp_table_floats(h->dc);
+                std::memcpy(&bits[m], &off, sizeof(off));
+            }
+            if (int rc = upload_small(h, reinterpret_cast<float*>(p.member_off.p), bits, MPPI_MAX_PARTICLES, s)) return rc;
+            p.member_off_valid = true;
+        }
+        ctx.ref = h->model.mlp.p;
+        ctx.pad = reinterpret_cast<const uint8_t*>(p.member_off.p);
+        ctx.pad_stride = p.P;
+    }
     const bool gen = regen_noise(h);
     if (!gen && !h->core.tiles_valid) return fail(h, MPPI_E_STATE, "no noise: call mppi_sample or mppi_inject_noise first");
     {
@@ -61,7 +88,7 @@ int rollout_particles(mppi_handle_t h, hipStream_t s) {
         tm.launch(gen ? rollout_particles_kernel<MODEL, FASTV, true, UCV> : rollout_particles_kernel<MODEL, FASTV, false, UCV>, \
                   grid, dim3(BLOCK), shmem, (const float4*)h->core.noise.p, (const float*)h->core.mean.p,                    \
                   (const float*)p.table.p, h->core.x0_cur, p.costs.p, h->core.mean_used.p, h->core.x0_used.p, h->d,         \
-                  h->core.gen, h->model.ctx);                                                         \
+                  h->core.gen, ctx);                                                                  \
     } while (0)
         MPPI_DISPATCH(h, CALL_PARTICLES);
 #undef CALL_PARTICLES
@@ -77,6 +104,7 @@ int rollout_particles(mppi_handle_t h, hipStream_t s) {
 int clone_particles(mppi_handle_t dst, mppi_handle_t src) {
     auto &dp = dst->part, &sp = src->part;
     dp.P = sp.P; dp.mode = sp.mode; dp.k = sp.k; dp.costs_valid = false;
+    dp.members = sp.members; dp.member_off_valid = false;  // (the offsets are staged again by dst's next rollout)
     if (sp.table) {
         if (!dp.table) HIP_TRY(dst, dp.table.alloc(sp.table.n));
         HIP_TRY(dst, hipMemcpy(dp.table.p, sp.table.p, sizeof(float) * sp.table.n, hipMemcpyDeviceToDevice));
@@ -102,6 +130,8 @@ int mppi_set_particles(mppi_handle_t h, const float* particles, int P, int on_de
     if (P == 0 || !particles) {  // off
         p.P = 0;
         p.costs_valid = false;
+        p.members.clear();  // (the map belongs to the particles it was given for)
+        p.member_off_valid = false;
         return MPPI_OK;
     }
     if (h->opt.mapping == 1) return fail(h, MPPI_E_INVALID, "particles are not available with mapping = 1");
@@ -126,6 +156,31 @@ int mppi_get_particles(mppi_handle_t h, float* out, int* P_out, int on_device, v
     if (!h->part.table) return fail(h, MPPI_E_STATE, "generic handle: it records the particle count only");
     return copy_small(h, out, h->part.table.p, sizeof(float) * (size_t)h->part.P * (size_t)h->ds, on_device != 0, true,
                       (hipStream_t)stream);
+}
+
+int mppi_set_particle_members(mppi_handle_t h, const int* members, int P) {
+    if (!h) return MPPI_E_INVALID;
+    auto& p = h->part;
+    if (!members || P == 0) {  // none
+        p.members.clear();
+        p.member_off_valid = false;
+        return MPPI_OK;
+    }
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "particle members belong to the learned-dynamics models");
+    if (P < 0 || P > MPPI_MAX_PARTICLES) return fail(h, MPPI_E_INVALID, "particle members: 0 <= P <= MPPI_MAX_PARTICLES (16)");
+    for (int m = 0; m < P; ++m)
+        if (members[m] < 0 || members[m] >= MPPI_MAX_PARTICLES)
+            return fail(h, MPPI_E_INVALID, "particle members: every entry is a member index, 0 <= e < MPPI_MAX_PARTICLES (16)");
+    p.members.assign(members, members + P);  // (checked against P and the ensemble where the rollout is launched)
+    p.member_off_valid = false;
+    return MPPI_OK;
+}
+
+int mppi_get_particle_members(mppi_handle_t h, int* out, int* P_out) {
+    if (!h) return MPPI_E_INVALID;
+    if (P_out) *P_out = (int)h->part.members.size();
+    if (out) std::copy(h->part.members.begin(), h->part.members.end(), out);
+    return MPPI_OK;
 }
 
 int mppi_set_risk(mppi_handle_t h, int mode, int k) {

@@ -16,7 +16,8 @@
 //   capi_exchange.hip  RCCL loader, comm / p2p exchanges, time-out flags             (+ the p2p kernels)
 //   capi_covariance.hip  covariance adaptation: settings, the per-step sigma table, the step after the weights (mppi_variance.hpp)
 //   capi_colored.hip   temporally correlated noise: the setting, its per-column table, the filtered draws (mppi_sample.hpp)
-//   capi_particles.hip risk-aware solves: the particle table, the risk measure, the rollout from every particle and the fold
+//   capi_particles.hip risk-aware solves: the particle table, the risk measure, the rollout from every particle (each through
+//                      a member of an MLP ensemble of its own, where a map says so) and the fold
 //                      (mppi_particles.hpp: rollout_particles_kernel, particle_fold_kernel)
 // Kernel headers, one per stage.  A kernel that is not a template is defined in the one unit that launches it.
 //   mppi_common.hpp    Dims, GenCtx, wave reductions
@@ -238,6 +239,11 @@ struct MppiSolver {
         DevBuf<float> table;           // [MPPI_MAX_PARTICLES][ds] (native models; allocated on first use)
         DevBuf<float> costs;           // [P][N] of the last rollout (allocated on first use, grows on the set-up path)
         bool costs_valid = false;      // ... and whether a rollout / mppi_set_particle_costs has filled it for the current P
+        // the map from particle to ensemble member (mppi_set_particle_members; empty: none) and its device form: the member's
+        // offset into model.mlp in floats, [MPPI_MAX_PARTICLES], staged by the first rollout that uses the map
+        std::vector<int> members;
+        DevBuf<int32_t> member_off;
+        bool member_off_valid = false;
     } part;
 
     // temperature: statistics passes, the device-resident ESSPS / LBPS / Brent / MPO searches
@@ -310,7 +316,9 @@ struct MppiSolver {
         int ref_part_rows = 0;         // reference part: mppi_set_reference / mppi_ref_window
         int disc_part_rows = 0;        // disc part: mppi_set_discs
         float soft_reach = 2.0f, soft_skirt = 1.0f;  // the soft disc models' skirt as it was set (mppi_set_disc_softness)
-        DevBuf<float> mlp;             // weight table of the learned-dynamics models (mppi_set_mlp); ctx.ref points at it
+        DevBuf<float> mlp;             // weight tables of the learned-dynamics models [mlp_members][mlp_table_floats(dc)] (mppi_set_mlp:
+                                       // one; mppi_set_mlp_ensemble); ctx.ref points at member mlp_nominal's
+        int mlp_members = 0, mlp_nominal = 0;
         // device-resident reference window (mppi_set_center_path / mppi_ref_window)
         DevBuf<float> center8;         // [n][8] centre line with sin/cos of the yaw
         DevBuf<int32_t> win_dind;      // [rows] index offsets of the window rows
@@ -531,7 +539,7 @@ inline int check_ready(mppi_handle_t h) {
     if ((is_nav2d(m) || is_racing_model(m)) && !h->model.map_cells[0])
         return fail(h, MPPI_E_STATE, "obstacle map (slot 0) not uploaded");
     if (is_racing_model(m) && !h->model.map_cells[1]) return fail(h, MPPI_E_STATE, "lane map (slot 1) not uploaded");
-    if (is_mlp(m) && !h->model.ctx.ref) return fail(h, MPPI_E_STATE, "no weight table: call mppi_set_mlp first");
+    if (is_mlp(m) && !h->model.ctx.ref) return fail(h, MPPI_E_STATE, "no weight table: call mppi_set_mlp or mppi_set_mlp_ensemble first");
     // the step table (mppi_models.hpp): every part its layout has covers the horizon (ctx.ref is aimed at it once they do)
     const StepLayout L = step_layout(m);
     if (L.has_ref() && h->model.ref_part_rows < h->d.T)

@@ -63,6 +63,17 @@ constexpr int MLP_TWO_LAYERS = 1, MLP_TANH = 2, MLP_RESIDUAL = 4;
 constexpr int mlp_table_floats(int dc) {
     return MPPI_MLP_HIDDEN * (4 + dc) + MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN * MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN + 4 * MPPI_MLP_HIDDEN + 4;
 }
+// A member per particle (mppi_set_particle_members; rollout_particles_kernel only): the map rides in two more fields these
+// models leave free, for that one launch — ModelCtx::pad is the device table of the members' offsets into the weight buffer,
+// in floats, one int32 per particle (null: no map), ModelCtx::pad_stride its length.  Read at a block-uniform index through
+// the constant address space: one scalar load.
+#if defined(__HIP_DEVICE_COMPILE__)
+MPPI_HD const int32_t __attribute__((address_space(4)))* member_offsets(const ModelCtx& c) {
+    return (const int32_t __attribute__((address_space(4)))*)c.pad;
+}
+#else
+MPPI_HD const int32_t* member_offsets(const ModelCtx& c) { return reinterpret_cast<const int32_t*>(c.pad); }
+#endif
 
 // The step table: the models whose cost reads step-constant values carry ONE table with one row per horizon step.  It is
 // ModelCtx::ref, ref_rows is the number of rows every part of it covers (the solve checks it against the horizon), and the

@@ -206,3 +206,122 @@ class MLPModel:
         for a in (new.goal, new.q, new.r):
             a.flags.writeable = False
         return new
+
+
+MAX_MEMBERS = 16  # MPPI_MAX_PARTICLES: a member per particle
+
+
+class MLPEnsemble:
+    """A bootstrap ensemble of learned models: E networks of ONE architecture and one cost, as an MPPI plugin.
+
+        ens = MLPEnsemble.from_modules([net0, net1, ...], goal=[...], q=[...], r=[...])
+        solver = MPPI(dim_state=4, dim_control=dc, dynamics=ens.dynamics, cost_func=ens.cost, risk="cvar", risk_alpha=0.4, ...)
+        solver.set_model_particles("all")        # every sample is scored under every member, the costs folded by `risk`
+
+    `dynamics` / `cost` are the NOMINAL member's plain torch callables (tag "mlp41" / "mlp42"): every solve without
+    particles, the returned `state_seq` and every re-roll evaluate that one network.  The other members decide particle
+    costs only (pi_mpc.mppi.MPPI: set_model_particles, set_state_particles(..., members=)); on the device they are one
+    buffer of E tables (include/mppi_hip.h: mppi_set_mlp_ensemble), each padded exactly as MLPModel pads its own."""
+
+    def __init__(self, members: Sequence[MLPModel], nominal: int = 0):
+        members = list(members)
+        if not 1 <= len(members) <= MAX_MEMBERS or not all(isinstance(m, MLPModel) for m in members):
+            raise ValueError(f"an ensemble of 1..{MAX_MEMBERS} MLPModel members (got {len(members)})")
+        first = members[0]
+        for m in members[1:]:
+            for name in ("dim_state_model", "dim_control", "hidden_layers", "activation", "residual"):
+                if getattr(m, name) != getattr(first, name):
+                    raise ValueError(f"the members of an ensemble share one architecture: {name} differs "
+                                     f"({getattr(m, name)!r} against {getattr(first, name)!r})")
+            if not all(np.array_equal(getattr(m, n), getattr(first, n)) for n in ("goal", "q", "r")):
+                raise ValueError("the members of an ensemble share one cost: goal, q and r must be equal (set_cost sets all)")
+        self._members = members
+        self._nominal = self._check_index(nominal)
+        self._nominal_version = 0
+        self._stack = None  # (member versions, the stacked tables [E, n])
+
+    @classmethod
+    def from_modules(cls, modules: Sequence[torch.nn.Module], nominal: int = 0, **kw) -> "MLPEnsemble":
+        """One MLPModel.from_module(net, **kw) per network (goal=, q=, r=, residual=: the same for all)."""
+        return cls([MLPModel.from_module(m, **kw) for m in modules], nominal=nominal)
+
+    def _check_index(self, e) -> int:
+        if isinstance(e, bool) or int(e) != e or not 0 <= int(e) < len(self._members):
+            raise ValueError(f"member index {e!r}: the ensemble has members 0..{len(self._members) - 1}")
+        return int(e)
+
+    # ------------------------------------------------------------------ members
+    @property
+    def n_members(self) -> int:
+        return len(self._members)
+
+    @property
+    def nominal(self) -> int:
+        return self._nominal
+
+    def member(self, e: int) -> MLPModel:
+        """Member e's MLPModel (its callables run anywhere, the solver's generic path included)."""
+        return self._members[self._check_index(e)]
+
+    def set_nominal(self, e: int) -> None:
+        """Which member `dynamics` / `cost` and everything outside the particle rollout evaluate, from the next solve on."""
+        e = self._check_index(e)
+        if e != self._nominal:
+            self._nominal = e
+            self._nominal_version += 1
+
+    def update_weights(self, e: int, weights: Sequence, biases: Sequence) -> None:
+        """New weights of the same shapes for member e (a model learned online); the solver uploads that member's table only."""
+        self._members[self._check_index(e)].update_weights(weights, biases)
+
+    def set_cost(self, goal=None, q=None, r=None) -> None:
+        """MLPModel.set_cost for every member: there is one cost."""
+        for m in self._members:
+            m.set_cost(goal=goal, q=q, r=r)
+
+    @property
+    def version(self) -> int:
+        """Moves whenever a member's weights or the nominal index changed."""
+        return sum(m.version for m in self._members) + self._nominal_version
+
+    @property
+    def tables(self) -> np.ndarray:
+        """The members' tables stacked, float32 [E, n] (row e is member(e).table)."""
+        key = tuple(m.version for m in self._members)
+        if self._stack is None or self._stack[0] != key:
+            self._stack = (key, np.ascontiguousarray(np.stack([m.table for m in self._members]), dtype=np.float32))
+        return self._stack[1]
+
+    # ------------------------------------------------------------------ what the solver asks for
+    @property
+    def model_name(self) -> str:
+        return self._members[0].model_name
+
+    def __getattr__(self, name):  # (the architecture, as the members state it)
+        if name in ("dim_state_model", "dim_control", "hidden_layers", "activation", "residual", "goal", "q", "r"):
+            return getattr(self.__dict__["_members"][self.__dict__["_nominal"]], name)
+        raise AttributeError(name)
+
+    def native_inputs(self) -> dict:
+        spec = self._members[self._nominal].native_inputs()
+        spec["mlp"].update(tables=self.tables, nominal=self._nominal, version=self.version,
+                           member_versions=tuple(m.version for m in self._members))
+        return spec
+
+    # ------------------------------------------------------------------ the callables: the nominal member's
+    @native_model(lambda owner: owner.model_name, "dynamics")
+    def dynamics(self, state: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
+        return self._members[self._nominal].dynamics(state, action)
+
+    @native_model(lambda owner: owner.model_name, "cost", _provider)
+    def cost(self, state: torch.Tensor, action: torch.Tensor, info=None) -> torch.Tensor:
+        return self._members[self._nominal].cost(state, action, info)
+
+    def __deepcopy__(self, memo):
+        import copy
+
+        new = object.__new__(type(self))
+        memo[id(self)] = new
+        new.__dict__.update(_members=[copy.deepcopy(m, memo) for m in self._members], _nominal=self._nominal,
+                            _nominal_version=self._nominal_version, _stack=None)
+        return new

@@ -48,7 +48,7 @@ class ModuleProtocolMixin:
         # host-side dynamic state
         for k in ("_solve_idx", "_lambda_value", "_last_lambda_value", "_lambda_override", "_used_known", "_essps_prev",
                   "_params_set", "_fused_error_seen", "_auto_params_sent", "_lbps_delta", "_essps_target_ess", "_lambda_min",
-                  "_lambda_max", "_risk", "_risk_alpha", "_particles_P"):
+                  "_lambda_max", "_risk", "_risk_alpha", "_particles_P", "_particle_members", "_model_particles"):
             it[k] = me[k]
         it["_lambda_pending"], it["_lambda_stream"] = False, None
         for k in ("_previous_action_seq", "_action_out", "_state_out", "_stats", "_summary", "_mean_of_last_solve", "_injected",
@@ -98,6 +98,9 @@ class ModuleProtocolMixin:
         out["noise_beta"] = self.noise_beta
         parts = self.state_particles  # risk-aware solves: the measure, and the particle table while one is set
         out["risk"], out["risk_alpha"], out["particles"] = self._risk, self._risk_alpha, None if parts is None else parts.cpu()
+        # an MLPEnsemble's members as particles: the map of an explicit table, or the sticky mode (set_model_particles)
+        out["particle_members"] = None if self._particle_members is None else list(self._particle_members)
+        out["model_particles"] = None if self._model_particles is None else list(self._model_particles)
         if self._rule_on_device == "ESSPS":  # the warm start of the device-resident search: the grid its last search left behind
             n = C.c_int64(0)
             self._h.call("mppi_essps_get_state", None, C.byref(n))
@@ -138,7 +141,14 @@ class ModuleProtocolMixin:
             self.set_noise_beta(state["noise_beta"])
         if state.get("risk") is not None:  # (absent in a state written before the setting existed: it stays as constructed)
             self.set_risk(state["risk"], state.get("risk_alpha"))
-            self.set_state_particles(state.get("particles"))
+            if state.get("model_particles") is not None:  # (the mode: the next forward() writes its own table)
+                self.set_model_particles(state["model_particles"])
+            else:
+                self.set_model_particles(None)
+                if state.get("particles") is None:
+                    self.set_state_particles(None)
+                else:
+                    self.set_state_particles(state["particles"], members=state.get("particle_members"))
         if state.get("cpu_generator") is not None and self._cpu_gen is not None:
             self._cpu_gen.set_state(state["cpu_generator"])
         if state.get("mpo") is not None and self._auto_lambda == "MPO":

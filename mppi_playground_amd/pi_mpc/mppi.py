@@ -196,7 +196,10 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                 matrix.  forward(state) is unchanged: `state` stays the nominal estimate, `state_seq` and every re-roll start
                 from it — the particles decide costs only.  Small problems take the multi-kernel sequence while particles are
                 set.  set_risk() changes the measure between solves, reset() keeps it and drops the particles, deepcopy and
-                state_dict() carry both.  Opaque callables run their two loops once per particle (with graph_callables the
+                state_dict() carry both.  With an envs.MLPEnsemble model the particles may stand for MODEL uncertainty: a member
+                of the ensemble per particle (set_state_particles(particles, members=...)), or set_model_particles("all") —
+                every forward(state) then scores all samples from `state` under each member (each rollout carried through one
+                network) in the one particle launch.  Opaque callables run their two loops once per particle (with graph_callables the
                 captured graph is replayed once per particle: it reads the start state from a static buffer) and one more
                 dynamics-only pass from the nominal state for `_state_seq_batch`.  ValueError for an unknown measure or
                 risk_alpha outside (0, 1].
@@ -239,6 +242,8 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         self._risk, self._risk_alpha = _host.check_risk_args(risk, risk_alpha)
         self._particles_P = 0        # start states set with set_state_particles (0: none — the plain solve)
         self._particles_keep = None  # the table as it was handed over (alive until the copy ran; the generic path reads it)
+        self._particle_members = None  # the map from particle to ensemble member the handle holds (a tuple), or None
+        self._model_particles = None   # set_model_particles: the members every forward(state) scores under (a tuple), or None
         dev = torch.device(device)
         if dev.type != "cuda":
             raise ValueError(f"device={dev}: this MPPI runs its hot path on MI355X only; there is no CPU path "
@@ -595,7 +600,12 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                 self._h.call("mppi_set_model_params", arr, len(p))
                 self._params_set = p
         mlp = spec.get("mlp")
-        if mlp is not None:  # learned dynamics: the weight table travels again whenever its owner bumped the version
+        if mlp is not None and "tables" in mlp:  # an ensemble: all tables once, then only what its owner changed
+            key = (id(self._cost_owner), mlp["version"])
+            if getattr(self._h, "mlp_key", None) != key:
+                self._put_mlp_ensemble(mlp)
+                self._h.mlp_key = key
+        elif mlp is not None:  # learned dynamics: the weight table travels again whenever its owner bumped the version
             key = (id(self._cost_owner), mlp["version"])
             if getattr(self._h, "mlp_key", None) != key:  # (kept on the handle: a new handle starts without a table)
                 tab = np.ascontiguousarray(mlp["table"], dtype=np.float32)
@@ -624,6 +634,26 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             r = np.ascontiguousarray(ref, dtype=np.float32)
             self._h.call("mppi_set_reference", r.ctypes.data_as(C.c_void_p), r.shape[0], self._stream())
             self._ref_uploaded = ref
+
+    def _put_mlp_ensemble(self, mlp) -> None:
+        """An MLPEnsemble's tables -> the handle, on the current stream with no host wait: all E of them the first time (and
+        whenever the ensemble is another one), afterwards only the members whose version moved (mppi_set_mlp_member) and the
+        nominal index (mppi_set_mlp_nominal).  What the handle holds is kept ON the handle, like the single table's key."""
+        h = self._h
+        tabs = np.ascontiguousarray(mlp["tables"], dtype=np.float32)
+        E, n = tabs.shape
+        versions, nominal = tuple(mlp["member_versions"]), int(mlp["nominal"])
+        held = getattr(h, "mlp_members", None)  # (id of the owner, member versions, nominal)
+        if held is None or held[0] != id(self._cost_owner) or len(held[1]) != E:
+            h.call("mppi_set_mlp_ensemble", tabs.ctypes.data_as(C.c_void_p), E, n, int(mlp["hidden_layers"]),
+                   _capi.MLP_ACTIVATIONS[mlp["activation"]], int(bool(mlp["residual"])), nominal, self._stream())
+        else:
+            for e in range(E):
+                if versions[e] != held[1][e]:
+                    h.call("mppi_set_mlp_member", e, tabs[e].ctypes.data_as(C.c_void_p), n, self._stream())
+            if nominal != held[2]:
+                h.call("mppi_set_mlp_nominal", nominal)
+        h.mlp_members = (id(self._cost_owner), versions, nominal)
 
     def _put_discs(self, table) -> None:
         """The moving-disc table [rows, n, 4] = {cx, cy, r2, w} per horizon step -> the handle (mppi_set_discs, on the
@@ -758,18 +788,26 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         self.set_state_particles(None)  # (the risk measure stays)
 
     # ------------------------------------------------------------------ risk-aware solves
-    def set_state_particles(self, particles) -> None:
+    def set_state_particles(self, particles, members=None) -> None:
         """The set of start states the next solves score every sample from: a [P, dim_state] tensor (device or host) or array,
         1 <= P <= 16 — a filter's particles, draws round an estimate; call it every tick.  None switches the feature off (the
         next solve is the plain one).  On the current stream, no host wait: a tensor on the solver's device is copied there,
         anything else goes through the pinned staging ring.  ValueError for a wrong shape or P > 16 (before the handle is
-        touched).  Works with every noise source (the torch-CPU draw is injected as tiles, which the particle rollout reads)."""
+        touched).  Works with every noise source (the torch-CPU draw is injected as tiles, which the particle rollout reads).
+        members (an envs.MLPEnsemble model only): P member indices in [0, E) — particle m is rolled out through ensemble member
+        members[m]; None (default): every particle through the nominal member, exactly as without an ensemble.  ValueError for
+        a model that is no MLPEnsemble, opaque callables, an index out of range or a length that is not P.  An explicit table
+        ends set_model_particles' mode (the later call wins); None leaves that mode alone (reset() calls it)."""
         if particles is None:
+            if self.__dict__.get("_model_particles") is not None:  # (a setting, not a table: nothing to drop)
+                return
             if self._particles_P:
-                self._h.call("mppi_set_particles", None, 0, 0, self._stream())
-            self._particles_P, self._particles_keep = 0, None
+                self._h.call("mppi_set_particles", None, 0, 0, self._stream())  # (drops the handle's member map too)
+            self._particles_P, self._particles_keep, self._particle_members = 0, None, None
             return
         P = _host.check_particles_shape(particles.shape, self._dim_state)
+        members = self._check_members(members, P)
+        self._model_particles = None
         st = self._stream()
         on_device = torch.is_tensor(particles) and particles.is_cuda and particles.device == self._device
         if on_device or self._model is None:  # (the generic path replaces the callables' start state on the device)
@@ -784,7 +822,81 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             self._h.call("mppi_set_particles", host.ctypes.data_as(C.c_void_p), P, 0, st)
             self._particles_keep = None
         self._particles_P = P
+        self._push_members(members)
         self._push_risk()
+
+    def _check_members(self, members, P=None):
+        """`members` as a tuple of ensemble member indices (None stays None); ValueError for what cannot work."""
+        if members is None:
+            return None
+        if self._model is None:
+            raise ValueError("members: opaque callables cannot know the ensemble member (the fused MLPEnsemble model only)")
+        E = getattr(self._cost_owner, "n_members", None)
+        if E is None:
+            raise ValueError("members: the model is no envs.MLPEnsemble")
+        if isinstance(members, str):
+            if members != "all":
+                raise ValueError("members: 'all', a sequence of member indices, or None")
+            members = range(E)
+        out = tuple(int(e) for e in (members.tolist() if hasattr(members, "tolist") else members))
+        if P is not None and len(out) != P:
+            raise ValueError(f"members: {len(out)} entries for {P} particles")
+        if not 1 <= len(out) <= _capi.MAX_PARTICLES:
+            raise ValueError(f"members: 1..{_capi.MAX_PARTICLES} entries")
+        if any(not 0 <= e < E for e in out):
+            raise ValueError(f"members: every entry is a member index in [0, {E})")
+        return out
+
+    def _push_members(self, members) -> None:
+        """Hand the map to the handle when it changed (None with none held: no call at all)."""
+        if members == self._particle_members:
+            return
+        if members is None:
+            self._h.call("mppi_set_particle_members", None, 0)
+        else:
+            self._h.call("mppi_set_particle_members", (C.c_int * len(members))(*members), len(members))
+        self._particle_members = members
+
+    def set_model_particles(self, members) -> None:
+        """Model uncertainty as particles (an envs.MLPEnsemble model): a STICKY mode in which every later forward(state) scores
+        all samples from `state` under each listed ensemble member — one particle per network, every rollout carried through
+        one member — and folds the costs by `risk`.  members: "all", a sequence of member indices (at most 16), or None for
+        off.  The [P, dim_state] table is written from `state` on the device every tick (no host wait); `state_seq` and every
+        re-roll stay the nominal member's.  Excludes an explicit particle table (the later call wins); reset() keeps the mode;
+        deepcopy and state_dict() carry it.  ValueError as for set_state_particles(..., members=)."""
+        if members is None:
+            if self._model_particles is not None:
+                self._model_particles = None
+                self.set_state_particles(None)
+            return
+        members = self._check_members(members)
+        self._model_particles = members
+        self._particles_P, self._particles_keep = len(members), None
+        self._push_members(members)
+        self._push_risk()
+
+    def _write_model_particles(self, state) -> None:
+        """set_model_particles' table for this tick: `state` once per listed member, built and copied on the device."""
+        P = len(self._model_particles)
+        row = torch.as_tensor(state).detach().to(self._device, self._dtype).reshape(1, self._dim_state)
+        self._particles_keep = row.repeat(P, 1)  # (alive until the next table: the copy reads it in stream order)
+        self._h.call("mppi_set_particles", _ptr(self._particles_keep), P, 1, self._stream())
+
+    @property
+    def particle_members(self) -> Optional[Tuple[int, ...]]:
+        """The map from particle to ensemble member the library holds (a tuple of P indices), or None while there is none."""
+        n = C.c_int(0)
+        self._h.call("mppi_get_particle_members", None, C.byref(n))
+        if not n.value:
+            return None
+        out = (C.c_int * n.value)()
+        self._h.call("mppi_get_particle_members", out, None)
+        return tuple(int(v) for v in out)
+
+    @property
+    def model_particles(self) -> Optional[Tuple[int, ...]]:
+        """The members set_model_particles listed, or None while that mode is off."""
+        return self._model_particles
 
     def _push_risk(self) -> None:
         k = _host.risk_k(self._risk_alpha, self._particles_P) if self._particles_P else 1
@@ -891,6 +1003,8 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
           _solve_generic    opaque `dynamics` / `cost_func` callables around the library's sampler / softmax / reduction.
         Injected noise (parity hook) sends a one-call solver through the entry points for that one solve."""
         assert state.shape == (self._dim_state,)
+        if self._model_particles is not None:
+            self._write_model_particles(state)
         if self._injected is not None and self._one_call:
             out = self._solve_by_steps(state, info)
         else:

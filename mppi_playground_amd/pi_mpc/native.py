@@ -13,7 +13,9 @@ where `provider(owner)` returns the model's current inputs as plain host data:
      "discs": {"table": float32 [rows, n, 4] = {cx, cy, r2, w} per horizon step (a torch tensor on the solver's device, or
                an ndarray), "version": int,
                "soft": {"reach": float > 1, "skirt": float in [0, 1]}  (the soft disc models only)}}
-("mlp": the learned-dynamics models only; "discs": the moving-disc models only — "nav2d_discs" (envs.MovingObstacleNav2DEnv)
+("mlp": the learned-dynamics models only — an ensemble (envs.MLPEnsemble) adds "tables": float32 [E, n] (row e: member e's
+table), "nominal": the member "table" is, and "member_versions": one version per member, so that the solver re-uploads only the
+members that changed; "discs": the moving-disc models only — "nav2d_discs" (envs.MovingObstacleNav2DEnv)
 and "racing_discs" (envs.racing_opponents: opponent cars, next to racing's "ref_path" or device-built window) — rows >= the
 horizon and n <= 8 or the solver raises ValueError; either table is uploaded again when its `version` changes.  "soft": the
 graded skirt of "nav2d_discs_soft" / "racing_discs_soft" (envs.SoftMovingObstacleNav2DEnv, envs.racing_opponents'
