@@ -65,7 +65,10 @@ enum {
     MPPI_MODEL_NAV2D_DISCS = 9, /* MPPI_MODEL_NAV2D + up to MPPI_MAX_DISCS moving disc obstacles (mppi_set_discs) */
     MPPI_MODEL_RACING_DISCS = 10, /* MPPI_MODEL_RACING + up to MPPI_MAX_DISCS moving disc obstacles: opponent cars (mppi_set_discs) */
     MPPI_MODEL_NAV2D_DISCS_SOFT = 11,  /* MPPI_MODEL_NAV2D_DISCS with a graded penalty skirt round every disc (mppi_set_disc_softness) */
-    MPPI_MODEL_RACING_DISCS_SOFT = 12  /* MPPI_MODEL_RACING_DISCS with the same skirt */
+    MPPI_MODEL_RACING_DISCS_SOFT = 12, /* MPPI_MODEL_RACING_DISCS with the same skirt */
+    MPPI_MODEL_MLP81 = 13,      /* learned dynamics: the MLP of MPPI_MODEL_MLP41 with 8 states, 1 control (mppi_set_mlp) */
+    MPPI_MODEL_MLP82 = 14,      /* the same with 2 controls                                           */
+    MPPI_MODEL_MLP84 = 15       /* the same with 4 controls                                           */
 };
 
 /* Racing parameter vector (mppi_set_model_params), racing_env.py:37-42,341-370, racing.py:41-46 */
@@ -85,13 +88,16 @@ enum { MPPI_GP_VMIN = 0, MPPI_GP_VMAX, MPPI_GP_WMIN, MPPI_GP_WMAX, MPPI_GP_DT, M
 /* Learned-dynamics (MLP) cost parameters: c = sum_m q[m] * (s[m] - g[m])^2 + sum_k r[k] * u[k]^2 (mppi_set_mlp has the
  * arithmetic): g[4], q[4], r[dim_control] -> 9 values for MPPI_MODEL_MLP41, 10 for MPPI_MODEL_MLP42 */
 enum { MPPI_MP_G = 0, MPPI_MP_Q = 4, MPPI_MP_R = 8, MPPI_MP_COUNT41 = 9, MPPI_MP_COUNT42 = 10 };
+/* The same for the 8-state ids: g[8], q[8], r[dim_control] -> 17 values for MPPI_MODEL_MLP81, 18 for MPPI_MODEL_MLP82, 20 for
+ * MPPI_MODEL_MLP84 */
+enum { MPPI_MP8_G = 0, MPPI_MP8_Q = 8, MPPI_MP8_R = 16, MPPI_MP8_COUNT81 = 17, MPPI_MP8_COUNT82 = 18, MPPI_MP8_COUNT84 = 20 };
 #define MPPI_MLP_HIDDEN 32 /* hidden width of the table; narrower layers are zero-padded by the caller */
 /* mppi_set_mlp `activation` */
 enum { MPPI_MLP_RELU = 0, MPPI_MLP_TANH = 1 };
 
 #define MPPI_MAX_PARAMS 32
 #define MPPI_MAX_DIM_STATE 8
-#define MPPI_MAX_DIM_CONTROL 4          /* controls held by MppiConfig (all native models have 1 or 2)       */
+#define MPPI_MAX_DIM_CONTROL 4          /* controls held by MppiConfig (native models: 1, 2 or 4)            */
 #define MPPI_MAX_DIM_CONTROL_GENERIC 64 /* MPPI_MODEL_GENERIC: any dim_control up to this (mppi.py:96-98)    */
 #define MPPI_SUMMARY_HEAD 4 /* {min cost, sum e, sum e^2, sum e*c} */
 
@@ -195,7 +201,12 @@ int mppi_set_reference(mppi_handle_t h, const float* ref_host, int rows, void* s
  * solves (a model learned online: every tick); a lazily completed state sequence is completed with the old weights first.
  * MPPI_E_INVALID for another model's handle, a wrong count, a flag out of range or a value that is not finite.  Solves on
  * an MLP handle without a table return MPPI_E_STATE.  mppi_clone_state copies table and flags; mppi_model_step does not
- * take these models (MPPI_E_INVALID: it has no handle to take the table from). */
+ * take these models (MPPI_E_INVALID: it has no handle to take the table from).
+ * MPPI_MODEL_MLP81 / MLP82 / MLP84 are the same network with DS = 8 states and dc = 1 / 2 / 4 controls: read 8 for every 4
+ * above (x = [s[0..7], u[0..dc-1]], m = 0..7, IN = 8 + dc, the parameters MPPI_MP8_*), the table in the same order
+ *     W1[32][IN], b1[32], W2[32][32], b2[32], W3[8][32], b3[8]
+ * of n_floats = 32*IN + 32 + 32*32 + 32 + 8*32 + 8 = 1640 / 1672 / 1736 values; a model with fewer than eight states is
+ * padded the same way.  Same operation order, same flags, same entry points (ensembles and particle members included). */
 int mppi_set_mlp(mppi_handle_t h, const float* table_host, int n_floats, int hidden_layers, int activation, int residual,
                  void* stream);
 /* Model ensembles for the learned dynamics: E = n_members networks of ONE architecture (one set of flags), each a table as
@@ -518,7 +529,7 @@ int mppi_set_risk(mppi_handle_t h, int mode, int k);
 int mppi_get_risk(mppi_handle_t h, int* mode_out, int* k_out);
 int mppi_get_particle_costs(mppi_handle_t h, float* out /* [P][N] */, int on_device, void* stream);
 int mppi_set_particle_costs(mppi_handle_t h, const float* src /* [P][N] */, int on_device, void* stream);
-/* The map from particle to ensemble member (MPPI_MODEL_MLP41 / MLP42 with mppi_set_mlp_ensemble): members[P], particle m is
+/* The map from particle to ensemble member (the MPPI_MODEL_MLP* ids with mppi_set_mlp_ensemble): members[P], particle m is
  * rolled out through member members[m]; NULL or P = 0: no map (every particle through the nominal member — the launch is
  * exactly the one without this feature).  Either this call or mppi_set_particles may come first: the rollout checks, before
  * anything is launched, that the map's length is the particle count and that every entry is < E (else MPPI_E_INVALID).

@@ -16,10 +16,12 @@ MODEL_GENERIC = -1
 MAX_DIM_CONTROL = 4           # controls held by MppiConfig
 MAX_DIM_CONTROL_GENERIC = 64  # opaque callables: any dim_control up to this
 MODEL_IDS = {"pendulum": 0, "cartpole": 1, "mountaincar": 2, "nav2d": 3, "racing": 4, "mjcartpole": 5, "goalzone": 6,
-             "mlp41": 7, "mlp42": 8, "nav2d_discs": 9, "racing_discs": 10, "nav2d_discs_soft": 11, "racing_discs_soft": 12}
+             "mlp41": 7, "mlp42": 8, "nav2d_discs": 9, "racing_discs": 10, "nav2d_discs_soft": 11, "racing_discs_soft": 12,
+             "mlp81": 13, "mlp82": 14, "mlp84": 15}
 MODEL_DIMS = {"pendulum": (2, 1), "cartpole": (4, 1), "mountaincar": (2, 1), "nav2d": (3, 2), "racing": (4, 2),
               "mjcartpole": (4, 1), "goalzone": (7, 2), "mlp41": (4, 1), "mlp42": (4, 2),
-              "nav2d_discs": (3, 2), "racing_discs": (4, 2), "nav2d_discs_soft": (3, 2), "racing_discs_soft": (4, 2)}
+              "nav2d_discs": (3, 2), "racing_discs": (4, 2), "nav2d_discs_soft": (3, 2), "racing_discs_soft": (4, 2),
+              "mlp81": (8, 1), "mlp82": (8, 2), "mlp84": (8, 4)}
 MLP_HIDDEN = 32               # MPPI_MLP_HIDDEN
 MLP_ACTIVATIONS = {"relu": 0, "tanh": 1}  # MPPI_MLP_*
 MAX_DISCS = 8                 # MPPI_MAX_DISCS

@@ -256,7 +256,7 @@ int mppi_set_mlp(mppi_handle_t h, const float* table, int n_floats, int hidden_l
                  void* stream) {
     if (!h || !table) return fail(h, MPPI_E_INVALID, "bad weight table");
     if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the weight table belongs to the learned-dynamics models");
-    if (n_floats != mlp_table_floats(h->dc)) return fail(h, MPPI_E_INVALID, "weight table: wrong number of values for this model");
+    if (n_floats != mlp_table_len(h)) return fail(h, MPPI_E_INVALID, "weight table: wrong number of values for this model");
     if (hidden_layers < 1 || hidden_layers > 2 || (activation != MPPI_MLP_RELU && activation != MPPI_MLP_TANH) ||
         (residual != 0 && residual != 1))
         return fail(h, MPPI_E_INVALID, "weight table: hidden_layers 1 or 2, activation relu or tanh, residual 0 or 1");
@@ -294,7 +294,7 @@ int mppi_set_mlp_ensemble(mppi_handle_t h, const float* tables, int n_members, i
     if (n_members < 1 || n_members > MPPI_MAX_PARTICLES)
         return fail(h, MPPI_E_INVALID, "weight tables: 1 <= n_members <= MPPI_MAX_PARTICLES (16)");
     if (nominal < 0 || nominal >= n_members) return fail(h, MPPI_E_INVALID, "weight tables: the nominal member is one of the n_members");
-    if (n_floats != mlp_table_floats(h->dc)) return fail(h, MPPI_E_INVALID, "weight table: wrong number of values for this model");
+    if (n_floats != mlp_table_len(h)) return fail(h, MPPI_E_INVALID, "weight table: wrong number of values for this model");
     if (hidden_layers < 1 || hidden_layers > 2 || (activation != MPPI_MLP_RELU && activation != MPPI_MLP_TANH) ||
         (residual != 0 && residual != 1))
         return fail(h, MPPI_E_INVALID, "weight table: hidden_layers 1 or 2, activation relu or tanh, residual 0 or 1");
@@ -323,7 +323,7 @@ int mppi_set_mlp_member(mppi_handle_t h, int e, const float* table, int n_floats
     if (!h->model.ctx.ref || h->model.mlp_members < 1)
         return fail(h, MPPI_E_STATE, "no weight table: call mppi_set_mlp or mppi_set_mlp_ensemble first");
     if (e < 0 || e >= h->model.mlp_members) return fail(h, MPPI_E_INVALID, "weight table: no such member");
-    if (n_floats != mlp_table_floats(h->dc)) return fail(h, MPPI_E_INVALID, "weight table: wrong number of values for this model");
+    if (n_floats != mlp_table_len(h)) return fail(h, MPPI_E_INVALID, "weight table: wrong number of values for this model");
     for (int i = 0; i < n_floats; ++i)
         if (!std::isfinite(table[i])) return fail(h, MPPI_E_INVALID, "weight table: every value must be finite");
     if (int rc = settle_state_seq(h)) return rc;  // a lazily completed state sequence belongs to the OLD weights: roll it out first
@@ -338,7 +338,7 @@ int mppi_set_mlp_nominal(mppi_handle_t h, int e) {
     if (e < 0 || e >= h->model.mlp_members) return fail(h, MPPI_E_INVALID, "nominal member: no such member");
     if (int rc = settle_state_seq(h)) return rc;  // a lazily completed state sequence belongs to the OLD nominal member
     h->model.mlp_nominal = e;
-    h->model.ctx.ref = h->model.mlp.p + (size_t)e * (size_t)mlp_table_floats(h->dc);
+    h->model.ctx.ref = h->model.mlp.p + (size_t)e * (size_t)mlp_table_len(h);
     return MPPI_OK;
 }
 

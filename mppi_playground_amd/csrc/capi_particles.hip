@@ -65,7 +65,7 @@ int rollout_particles(mppi_handle_t h, hipStream_t s) {
         if (!p.member_off_valid) {
             float bits[MPPI_MAX_PARTICLES] = {};  // (the int32 offsets, as the staging ring carries them)
             for (int m = 0; m < p.P; ++m) {
-                const int32_t off = p.members[(size_t)m] * mlp_table_floats(h->dc);
+                const int32_t off = p.members[(size_t)m] * mlp_table_len(h);
                 std::memcpy(&bits[m], &off, sizeof(off));
             }
             if (int rc = upload_small(h, reinterpret_cast<float*>(p.member_off.p), bits, MPPI_MAX_PARTICLES, s)) return rc;

@@ -126,7 +126,7 @@ __device__ __forceinline__ bool rollout_states_noise(const float* __restrict__ x
     // steps — a group is fetched where its first step runs, the step's inputs are picked with selects on the wave-uniform
     // position in the group — so that this walk holds one copy of the step instead of 4 / DC + 1 (see trajectory_cost).
     // Same operations per step, same order, same bits; the re-roll gives up the look-ahead of the noise chain.
-    if constexpr (MODEL == MPPI_MODEL_MLP41 || MODEL == MPPI_MODEL_MLP42) {
+    if constexpr (is_mlp(MODEL)) {
         auto pick4 = [](float a0, float a1, float a2, float a3, int i) {
             float r = a0;
             r = i == 1 ? a1 : r;

@@ -316,7 +316,7 @@ struct MppiSolver {
         int ref_part_rows = 0;         // reference part: mppi_set_reference / mppi_ref_window
         int disc_part_rows = 0;        // disc part: mppi_set_discs
         float soft_reach = 2.0f, soft_skirt = 1.0f;  // the soft disc models' skirt as it was set (mppi_set_disc_softness)
-        DevBuf<float> mlp;             // weight tables of the learned-dynamics models [mlp_members][mlp_table_floats(dc)] (mppi_set_mlp:
+        DevBuf<float> mlp;             // weight tables of the learned-dynamics models [mlp_members][mlp_table_floats(ds, dc)] (mppi_set_mlp:
                                        // one; mppi_set_mlp_ensemble); ctx.ref points at member mlp_nominal's
         int mlp_members = 0, mlp_nominal = 0;
         // device-resident reference window (mppi_set_center_path / mppi_ref_window)
@@ -398,6 +398,9 @@ inline bool model_dims(int model, ModelDims& md) {
     case MPPI_MODEL_RACING_DISCS: md = {4, 2}; return true;
     case MPPI_MODEL_NAV2D_DISCS_SOFT: md = {3, 2}; return true;
     case MPPI_MODEL_RACING_DISCS_SOFT: md = {4, 2}; return true;
+    case MPPI_MODEL_MLP81: md = {8, 1}; return true;
+    case MPPI_MODEL_MLP82: md = {8, 2}; return true;
+    case MPPI_MODEL_MLP84: md = {8, 4}; return true;
     }
     return false;
 }
@@ -409,9 +412,9 @@ inline bool is_nav2d(int model) {
 inline int model_param_count(int model) {
     return is_racing_model(model) ? MPPI_RP_COUNT : is_nav2d(model) ? MPPI_NP_COUNT
            : model == MPPI_MODEL_GOALZONE ? MPPI_GP_COUNT : model == MPPI_MODEL_MLP41 ? MPPI_MP_COUNT41
-           : model == MPPI_MODEL_MLP42 ? MPPI_MP_COUNT42 : 0;
+           : model == MPPI_MODEL_MLP42 ? MPPI_MP_COUNT42 : model == MPPI_MODEL_MLP81 ? MPPI_MP8_COUNT81
+           : model == MPPI_MODEL_MLP82 ? MPPI_MP8_COUNT82 : model == MPPI_MODEL_MLP84 ? MPPI_MP8_COUNT84 : 0;
 }
-inline bool is_mlp(int model) { return model == MPPI_MODEL_MLP41 || model == MPPI_MODEL_MLP42; }
 
 // Times one stage with a pair of HIP events (no host synchronisation); pairs accumulate until mppi_get_timing() drains
 // them.  The events ride on the stage's own dispatches (hipExtLaunchKernel): the start event on its first kernel launch,
@@ -529,8 +532,14 @@ inline int math_level(mppi_handle_t h) { return use_fast(h) ? (h->opt.math_fast 
         MPPI_DISPATCH_HW(MPPI_MODEL_RACING_DISCS, CALL)                                               \
         MPPI_DISPATCH_HW(MPPI_MODEL_NAV2D_DISCS_SOFT, CALL)                                           \
         MPPI_DISPATCH_HW(MPPI_MODEL_RACING_DISCS_SOFT, CALL)                                          \
+        MPPI_DISPATCH_NOHW(MPPI_MODEL_MLP81, CALL)                                                    \
+        MPPI_DISPATCH_NOHW(MPPI_MODEL_MLP82, CALL)                                                    \
+        MPPI_DISPATCH_NOHW(MPPI_MODEL_MLP84, CALL)                                                    \
         }                                                                                             \
     } while (0)
+
+// floats of one weight table of a learned-dynamics handle
+inline int mlp_table_len(mppi_handle_t h) { return mlp_table_floats(h->ds, h->dc); }
 
 inline int check_ready(mppi_handle_t h) {
     const int m = h->cfg.model;

@@ -56,13 +56,22 @@ struct ModelCtx {
     int32_t wrap_safe;     // per-step heading increments are < pi: wrapped angles stay in the narrow range
 };
 
-// The learned-dynamics models (MPPI_MODEL_MLP41 / MLP42; mppi_set_mlp): the weight table is ModelCtx::ref and the
-// launch-uniform flags ride in ModelCtx::ref_rows, two fields these models have no other use for, so the kernels'
+// The learned-dynamics models (MPPI_MODEL_MLP41 / MLP42 with 4 states, MLP81 / MLP82 / MLP84 with 8; mppi_set_mlp): the
+// weight table is ModelCtx::ref and the launch-uniform flags ride in ModelCtx::ref_rows, two fields these models have no other use for, so the kernels'
 // argument struct is what it was.
 constexpr int MLP_TWO_LAYERS = 1, MLP_TANH = 2, MLP_RESIDUAL = 4;
 constexpr int mlp_table_floats(int dc) {
     return MPPI_MLP_HIDDEN * (4 + dc) + MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN * MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN + 4 * MPPI_MLP_HIDDEN + 4;
 }
+// the same table for `ds` state components: W1[H][ds + dc], b1[H], W2[H][H], b2[H], W3[ds][H], b3[ds]
+constexpr int mlp_table_floats(int ds, int dc) {
+    return MPPI_MLP_HIDDEN * (ds + dc) + MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN * MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN + ds * MPPI_MLP_HIDDEN + ds;
+}
+static_assert(mlp_table_floats(4, 1) == mlp_table_floats(1) && mlp_table_floats(4, 2) == mlp_table_floats(2) &&
+              mlp_table_floats(8, 4) == 1736, "one layout for both state widths");
+// the ids of the learned-dynamics models
+constexpr bool is_mlp8(int model) { return model == MPPI_MODEL_MLP81 || model == MPPI_MODEL_MLP82 || model == MPPI_MODEL_MLP84; }
+constexpr bool is_mlp(int model) { return model == MPPI_MODEL_MLP41 || model == MPPI_MODEL_MLP42 || is_mlp8(model); }
 // A member per particle (mppi_set_particle_members; rollout_particles_kernel only): the map rides in two more fields these
 // models leave free, for that one launch — ModelCtx::pad is the device table of the members' offsets into the weight buffer,
 // in floats, one int32 per particle (null: no map), ModelCtx::pad_stride its length.  Read at a block-uniform index through
@@ -263,6 +272,7 @@ static_assert(krow_is_stride<MPPI_MODEL_PENDULUM>() && krow_is_stride<MPPI_MODEL
               krow_is_stride<MPPI_MODEL_NAV2D>() && krow_is_stride<MPPI_MODEL_RACING>() && krow_is_stride<MPPI_MODEL_MJCARTPOLE>() &&
               krow_is_stride<MPPI_MODEL_GOALZONE>() && krow_is_stride<MPPI_MODEL_MLP41>() && krow_is_stride<MPPI_MODEL_MLP42>() &&
               krow_is_stride<MPPI_MODEL_NAV2D_DISCS>() && krow_is_stride<MPPI_MODEL_RACING_DISCS>() &&
-              krow_is_stride<MPPI_MODEL_NAV2D_DISCS_SOFT>() && krow_is_stride<MPPI_MODEL_RACING_DISCS_SOFT>(),
+              krow_is_stride<MPPI_MODEL_NAV2D_DISCS_SOFT>() && krow_is_stride<MPPI_MODEL_RACING_DISCS_SOFT>() &&
+              krow_is_stride<MPPI_MODEL_MLP81>() && krow_is_stride<MPPI_MODEL_MLP82>() && krow_is_stride<MPPI_MODEL_MLP84>(),
               "a functor's KROW is the stride of step_layout(model)");
 }  // namespace mppi

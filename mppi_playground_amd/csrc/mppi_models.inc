@@ -673,7 +673,7 @@ struct Model<MPPI_MODEL_RACING_DISCS_SOFT, FAST> : Model<MPPI_MODEL_RACING_DISCS
 // multiply-adds.  Shape of the code (the step is inlined once per step of a float4 group, per drain half, in the epilogue
 // and per noise mode, so the network is NOT unrolled as a whole):
 //   two hidden layers: layer 1 unrolled over its 32 units (h1 lives in 32 statically indexed registers), then ONE rolled
-//     loop over j that forms h2[j] from h1, applies the activation and adds W3[m][j] * h2[j] into the four outputs;
+//     loop over j that forms h2[j] from h1, applies the activation and adds W3[m][j] * h2[j] into the DS outputs;
 //   one hidden layer:  one rolled loop over j that forms h1[j] from the IN inputs and adds W3[m][j] * h1[j].
 // Both visit every sum in ascending index order.  tanh at the fast levels: 1 - 2 / (e^(2z) + 1) with the hardware
 // exponential and reciprocal (e = inf and e = 0 give +-1: no validity range, `bad` is never raised).
@@ -700,14 +700,14 @@ typedef const float __attribute__((address_space(4)))* MlpTable;
 typedef const float* MlpTable;
 #endif
 
-template <int DCN, bool FAST>
+template <int DSN, int DCN, bool FAST>
 struct MlpModel {
     using K = NoStepConst;
     static constexpr int KROW = 0;
     static MPPI_HD K load_k(const float*, int) { return K{}; }
     static MPPI_HD void check_state(const ModelCtx&, const float*, bool&) {}
     static MPPI_HD void enter(float*) {}
-    static constexpr int DS = 4, DC = DCN, IN = DS + DC, H = MPPI_MLP_HIDDEN;
+    static constexpr int DS = DSN, DC = DCN, IN = DS + DC, H = MPPI_MLP_HIDDEN;
     // offsets into the table: W1[H][IN], b1[H], W2[H][H], b2[H], W3[DS][H], b3[DS]
     static constexpr int OB1 = H * IN, OW2 = OB1 + H, OB2 = OW2 + H * H, OW3 = OB2 + H, OB3 = OW3 + DS * H;
     static MPPI_HD void step(const ModelCtx& c, const float* s, const float* u, float* sn, float* ss, bool&, bool = false, bool = false) {
@@ -756,23 +756,35 @@ struct MlpModel {
             sn[m] = residual ? s[m] + o[m] : o[m];
         }
     }
+    // cost parameters g[DS], q[DS], r[DC]: MPPI_MP_* for 4 states, MPPI_MP8_* for 8
+    static constexpr int PG = 0, PQ = DS, PR = 2 * DS;
+    static_assert(DS == 4 ? (PG == MPPI_MP_G && PQ == MPPI_MP_Q && PR == MPPI_MP_R)
+                          : (DS == 8 && PG == MPPI_MP8_G && PQ == MPPI_MP8_Q && PR == MPPI_MP8_R),
+                  "the parameter layout of include/mppi_hip.h");
+    static_assert(PR + DC <= MPPI_MAX_PARAMS && OB3 + DS == mlp_table_floats(DS, DC), "parameters and table as the host sizes them");
     static MPPI_HD float cost(const ModelCtx& c, const K&, const float* s, const float* u, const float*, bool&) {
         const float* P = c.P;
         float a = 0.0f;
 #pragma unroll
         for (int m = 0; m < DS; ++m) {
-            const float d = s[m] - P[MPPI_MP_G + m];
-            a = a + P[MPPI_MP_Q + m] * (d * d);
+            const float d = s[m] - P[PG + m];
+            a = a + P[PQ + m] * (d * d);
         }
 #pragma unroll
-        for (int k = 0; k < DC; ++k) a = a + P[MPPI_MP_R + k] * (u[k] * u[k]);
+        for (int k = 0; k < DC; ++k) a = a + P[PR + k] * (u[k] * u[k]);
         return a;
     }
 };
 template <bool FAST>
-struct Model<MPPI_MODEL_MLP41, FAST> : MlpModel<1, FAST> {};
+struct Model<MPPI_MODEL_MLP41, FAST> : MlpModel<4, 1, FAST> {};
 template <bool FAST>
-struct Model<MPPI_MODEL_MLP42, FAST> : MlpModel<2, FAST> {};
+struct Model<MPPI_MODEL_MLP42, FAST> : MlpModel<4, 2, FAST> {};
+template <bool FAST>
+struct Model<MPPI_MODEL_MLP81, FAST> : MlpModel<8, 1, FAST> {};
+template <bool FAST>
+struct Model<MPPI_MODEL_MLP82, FAST> : MlpModel<8, 2, FAST> {};
+template <bool FAST>
+struct Model<MPPI_MODEL_MLP84, FAST> : MlpModel<8, 4, FAST> {};
 
 }  // namespace MPPI_MODEL_NS
 }  // namespace mppi

@@ -17,7 +17,7 @@ namespace mppi {
 // is added once, behind the fold).  Block (0, 0) writes the snapshots the plain kernel's block 0 writes: x0_used takes the
 // NOMINAL state (later re-rolls and finalize's state sequence start there), mean_used the mean.  No rider block, no stamps:
 // the stage is timed on its two dispatches.  The minimum key belongs to the fold.
-// The learned-dynamics models (MLP41 / MLP42 only, behind `if constexpr`: every other instantiation is the text above) may
+// The learned-dynamics models (the MLP ids only, behind `if constexpr`: every other instantiation is the text above) may
 // carry particle m through ensemble member members[m] (mppi_set_particle_members): the launch site hands the members'
 // offsets into the weight buffer in ctx.pad (mppi_models.hpp: member_offsets), the block reads its entry at a uniform address
 // and moves ITS copy of ctx.ref.  The cost of (i, m) is then what a plain handle holding that member's table computes.
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(BLOCK) void rollout_particles_kernel(const float4* 
     const bool inherit = (d.sample_offset + i) < d.inherit_count;
     const float4* np = noise + tile * d.R * 64 + lane;
     const float4* mp = inherit ? s_mean4 : s_mean4 + d.R;  // (RolloutLds::zeros, in float4 groups)
-    if constexpr (MODEL == MPPI_MODEL_MLP41 || MODEL == MPPI_MODEL_MLP42) {
+    if constexpr (is_mlp(MODEL)) {
         // a member per particle: the block's copy of the table pointer moves to its member's table (the step reads it through
         // the constant address space: scalar loads, as before).  No map: ctx.pad is null and the pointer stays where it was.
         ModelCtx mctx = ctx;

@@ -83,6 +83,9 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
     // The three-instruction u1 of box_muller (philox.hpp) keeps 2^-24 in a vector register.  The rollout kernels of the goal
     // zone sit at 80 VGPRs, the last count with six waves per SIMD, and the learned model's control-cost kernel at 96, the
     // last with five: with it they lose a wave (82 / 97), so these models draw with the four-instruction form, the same bits.
+    // The 8-state learned models take it: it costs each of their regenerating kernels one VGPR (mlp81 94 -> 95, mlp82 97 -> 98,
+    // mlp84 93 -> 94 at the fast level; 99 -> 100, 102 -> 103, 81 -> 82 with the library math; the control-cost kernels alike)
+    // and none of them crosses a step: the waves per SIMD are the same with either form (profiles/r25_mlp8.md).
     constexpr bool U1_FMA = MODEL != MPPI_MODEL_GOALZONE && MODEL != MPPI_MODEL_MLP41;
     if (GEN) asm volatile("" : "+v"(pins.k0v), "+v"(pins.k1v), "+v"(pins.k0w));
     float s[DS], pu[DC], pl[DC];
@@ -141,7 +144,7 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
     // copies, most of the instruction cache.  Their groups are walked by a ROLLED loop instead: the step's inputs are picked
     // from the group's registers with selects on the (wave-uniform) step index — three per value, against ~1300 multiply-adds
     // per step — and each of the three walks holds one copy.  Same operations per step in the same order.
-    constexpr bool ROLL_GROUP = MODEL == MPPI_MODEL_MLP41 || MODEL == MPPI_MODEL_MLP42;
+    constexpr bool ROLL_GROUP = is_mlp(MODEL);
     auto pick4 = [](float a0, float a1, float a2, float a3, int i) {  // (scalars: nothing here can be turned into an indexed load)
         float r = a0;
         r = i == 1 ? a1 : r;

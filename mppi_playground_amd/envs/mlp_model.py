@@ -9,7 +9,11 @@ tag "mlp41" / "mlp42" (by the control width), so that pi_mpc.mppi.MPPI runs them
 
 What the device path takes: a state of 4 components, 1 or 2 controls, one or two hidden layers of at most 32 units, relu or
 tanh.  Narrower layers and a narrower state are zero-padded here (rows, columns and biases: relu(0) = tanh(0) = 0 and adding
-w * 0 changes no bit of a sum); the CALLER pads the state vector it hands to the solver with components that stay zero.
+w * 0 changes no bit of a sum); the CALLER pads the state vector it hands to the solver with components that stay zero
+(pad_state does it; dim_state is the width the solver must be given).
+
+MLPModel8 is the same model with a state of 8 components and 1, 2 or 4 controls (tags "mlp81" / "mlp82" / "mlp84"): a cart
+with two poles, a planar quadrotor, anything with four actuators.  Read 8 for 4 below.
 
 The arithmetic, in fp32 and in this order (the torch code below, the device functor and tests/mlp_ref.py state the same):
     x = [s[0..3], u[0..dc-1]]          (u: the solver-clamped action, not clamped again)
@@ -28,7 +32,6 @@ import torch
 
 from pi_mpc.native import native_model
 
-DS = 4       # state components of the native models
 HIDDEN = 32  # hidden width of the device table (MPPI_MLP_HIDDEN)
 
 
@@ -43,6 +46,9 @@ def _provider(owner):
 
 
 class MLPModel:
+    DS = 4              # state components of the native models this class tags
+    CONTROLS = (1, 2)   # control widths they are compiled for
+
     def __init__(self, weights: Sequence, biases: Sequence, activation: str = "tanh", residual: bool = True, goal=None,
                  q=None, r=None):
         """weights / biases: per layer, torch.nn.Linear's layout — W1 [h1, ds + dc], (W2 [h2, h1],) W3 [ds, h] with
@@ -62,7 +68,7 @@ class MLPModel:
                 raise ValueError(f"{name} must hold {n} finite values")
             return a
 
-        goal4, q4 = np.zeros(DS, np.float32), np.zeros(DS, np.float32)
+        goal4, q4 = np.zeros(self.DS, np.float32), np.zeros(self.DS, np.float32)
         goal4[:ds] = vec(goal, ds, 0.0, "goal")
         q4[:ds] = vec(q, ds, 1.0, "q")
         # (read-only: the torch callables and the device both take them from here; set_cost() replaces them for both)
@@ -95,12 +101,14 @@ class MLPModel:
             raise ValueError("every weight is a matrix [out, in] with a bias [out]")
         if any(w.shape[1] != p.shape[0] for p, w in zip(Ws[:-1], Ws[1:])):
             raise ValueError("the layers do not chain: each weight's input width is the previous layer's output width")
+        DS = self.DS
         ds = Ws[-1].shape[0]
         dc = Ws[0].shape[1] - ds
         if not 1 <= ds <= DS:
             raise ValueError(f"the network's output (the state) has {ds} components: 1..{DS} run on the device")
-        if dc not in (1, 2):
-            raise ValueError(f"control width {dc} (input width {Ws[0].shape[1]} - state {ds}): 1 or 2 run on the device")
+        if dc not in self.CONTROLS:
+            raise ValueError(f"control width {dc} (input width {Ws[0].shape[1]} - state {ds}): "
+                             f"{', '.join(map(str, self.CONTROLS[:-1]))} or {self.CONTROLS[-1]} run on the device")
         if any(w.shape[0] > HIDDEN for w in Ws[:-1]):
             raise ValueError(f"hidden layers of at most {HIDDEN} units run on the device")
         if not all(np.all(np.isfinite(a)) for a in Ws + bs):
@@ -110,7 +118,7 @@ class MLPModel:
             raise ValueError("update_weights keeps the model's state width, control width and number of layers")
         self.dim_state_model, self.dim_control, self.hidden_layers = ds, dc, len(Ws) - 1
         IN = DS + dc
-        # the padded layers of the table: W1[32][IN], b1[32], W2[32][32], b2[32], W3[4][32], b3[4]
+        # the padded layers of the table: W1[32][IN], b1[32], W2[32][32], b2[32], W3[DS][32], b3[DS]
         W1 = np.zeros((HIDDEN, IN), np.float32)
         W1[:Ws[0].shape[0], :ds] = Ws[0][:, :ds]
         W1[:Ws[0].shape[0], DS:] = Ws[0][:, ds:]
@@ -149,7 +157,20 @@ class MLPModel:
     # ------------------------------------------------------------------ what the solver asks for
     @property
     def model_name(self) -> str:
-        return "mlp41" if self.dim_control == 1 else "mlp42"
+        return f"mlp{self.DS}{self.dim_control}"
+
+    @property
+    def dim_state(self) -> int:
+        """The state width of the native model: what MPPI(dim_state=...) must be given."""
+        return self.DS
+
+    def pad_state(self, x):
+        """A state of the network's own width (or any width up to dim_state), zero-padded to dim_state along its last axis."""
+        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float32))
+        n = t.shape[-1]
+        if n > self.DS:
+            raise ValueError(f"a state of {n} components does not fit the model's {self.DS}")
+        return t if n == self.DS else torch.nn.functional.pad(t, (0, self.DS - n))
 
     def native_inputs(self) -> dict:
         return {"params": [float(v) for v in np.concatenate([self.goal, self.q, self.r])],
@@ -181,7 +202,7 @@ class MLPModel:
             for i in range(HIDDEN):
                 z = z + W2[:, i] * h[:, i:i + 1]
             h = self._act(z)
-        o = b3.expand(x.shape[0], DS)
+        o = b3.expand(x.shape[0], self.DS)
         for j in range(HIDDEN):
             o = o + W3[:, j] * h[:, j:j + 1]
         return state + o if self.residual else o
@@ -190,7 +211,7 @@ class MLPModel:
     def cost(self, state: torch.Tensor, action: torch.Tensor, info=None) -> torch.Tensor:
         goal, q, r = self._on(state)[6:]
         c = torch.zeros(state.shape[0], device=state.device, dtype=state.dtype)
-        for m in range(DS):
+        for m in range(self.DS):
             d = state[:, m] - goal[m]
             c = c + q[m] * (d * d)
         for k in range(self.dim_control):
@@ -208,6 +229,13 @@ class MLPModel:
         return new
 
 
+class MLPModel8(MLPModel):
+    """MLPModel with a state of up to 8 components and 1, 2 or 4 controls: native tags "mlp81" / "mlp82" / "mlp84"
+    (MPPI(dim_state=8, ...)).  Same padding, same arithmetic, same interface; goal and q are kept with 8 entries."""
+    DS = 8
+    CONTROLS = (1, 2, 4)
+
+
 MAX_MEMBERS = 16  # MPPI_MAX_PARTICLES: a member per particle
 
 
@@ -218,8 +246,8 @@ class MLPEnsemble:
         solver = MPPI(dim_state=4, dim_control=dc, dynamics=ens.dynamics, cost_func=ens.cost, risk="cvar", risk_alpha=0.4, ...)
         solver.set_model_particles("all")        # every sample is scored under every member, the costs folded by `risk`
 
-    `dynamics` / `cost` are the NOMINAL member's plain torch callables (tag "mlp41" / "mlp42"): every solve without
-    particles, the returned `state_seq` and every re-roll evaluate that one network.  The other members decide particle
+    `dynamics` / `cost` are the NOMINAL member's plain torch callables (the members' tag: they are all MLPModel or all
+    MLPModel8): every solve without particles, the returned `state_seq` and every re-roll evaluate that one network.  The other members decide particle
     costs only (pi_mpc.mppi.MPPI: set_model_particles, set_state_particles(..., members=)); on the device they are one
     buffer of E tables (include/mppi_hip.h: mppi_set_mlp_ensemble), each padded exactly as MLPModel pads its own."""
 
@@ -228,6 +256,8 @@ class MLPEnsemble:
         if not 1 <= len(members) <= MAX_MEMBERS or not all(isinstance(m, MLPModel) for m in members):
             raise ValueError(f"an ensemble of 1..{MAX_MEMBERS} MLPModel members (got {len(members)})")
         first = members[0]
+        if any(type(m) is not type(first) for m in members[1:]):
+            raise ValueError("the members of an ensemble are of one class: all MLPModel or all MLPModel8")
         for m in members[1:]:
             for name in ("dim_state_model", "dim_control", "hidden_layers", "activation", "residual"):
                 if getattr(m, name) != getattr(first, name):
@@ -241,9 +271,10 @@ class MLPEnsemble:
         self._stack = None  # (member versions, the stacked tables [E, n])
 
     @classmethod
-    def from_modules(cls, modules: Sequence[torch.nn.Module], nominal: int = 0, **kw) -> "MLPEnsemble":
-        """One MLPModel.from_module(net, **kw) per network (goal=, q=, r=, residual=: the same for all)."""
-        return cls([MLPModel.from_module(m, **kw) for m in modules], nominal=nominal)
+    def from_modules(cls, modules: Sequence[torch.nn.Module], nominal: int = 0, model_class=MLPModel, **kw) -> "MLPEnsemble":
+        """One model_class.from_module(net, **kw) per network (goal=, q=, r=, residual=: the same for all); model_class:
+        MLPModel or MLPModel8."""
+        return cls([model_class.from_module(m, **kw) for m in modules], nominal=nominal)
 
     def _check_index(self, e) -> int:
         if isinstance(e, bool) or int(e) != e or not 0 <= int(e) < len(self._members):
@@ -298,7 +329,8 @@ class MLPEnsemble:
         return self._members[0].model_name
 
     def __getattr__(self, name):  # (the architecture, as the members state it)
-        if name in ("dim_state_model", "dim_control", "hidden_layers", "activation", "residual", "goal", "q", "r"):
+        if name in ("dim_state_model", "dim_control", "hidden_layers", "activation", "residual", "goal", "q", "r", "DS",
+                    "dim_state", "pad_state"):
             return getattr(self.__dict__["_members"][self.__dict__["_nominal"]], name)
         raise AttributeError(name)
 

@@ -35,7 +35,7 @@ import numpy as np
 @dataclass(frozen=True)
 class NativeTag:
     model: object                 # a key of _capi.MODEL_IDS ("pendulum", "racing", ...), or model(owner) -> such a key
-                                  # (resolve() calls it: envs/mlp_model.py picks "mlp41" / "mlp42" by its control width)
+                                  # (resolve() calls it: envs/mlp_model.py picks "mlp41" / "mlp42" / "mlp81" / ... by its widths)
     role: str                     # "dynamics" | "cost"
     provider: Optional[Callable]  # provider(owner) -> dict
     per_owner: bool = False       # the model name came from the owner (below): dynamics and cost must share ONE owner
