@@ -86,7 +86,8 @@ enum { MPPI_GP_VMIN = 0, MPPI_GP_VMAX, MPPI_GP_WMIN, MPPI_GP_WMAX, MPPI_GP_DT, M
        MPPI_GP_CY, MPPI_GP_RADIUS, MPPI_GP_PENALTY, MPPI_GP_COUNT };
 
 /* Learned-dynamics (MLP) cost parameters: c = sum_m q[m] * (s[m] - g[m])^2 + sum_k r[k] * u[k]^2 (mppi_set_mlp has the
- * arithmetic): g[4], q[4], r[dim_control] -> 9 values for MPPI_MODEL_MLP41, 10 for MPPI_MODEL_MLP42 */
+ * arithmetic; mppi_set_mlp_reference replaces g, q by a row per horizon step, mppi_set_mlp_angular wraps angle errors):
+ * g[4], q[4], r[dim_control] -> 9 values for MPPI_MODEL_MLP41, 10 for MPPI_MODEL_MLP42 */
 enum { MPPI_MP_G = 0, MPPI_MP_Q = 4, MPPI_MP_R = 8, MPPI_MP_COUNT41 = 9, MPPI_MP_COUNT42 = 10 };
 /* The same for the 8-state ids: g[8], q[8], r[dim_control] -> 17 values for MPPI_MODEL_MLP81, 18 for MPPI_MODEL_MLP82, 20 for
  * MPPI_MODEL_MLP84 */
@@ -232,6 +233,40 @@ int mppi_set_mlp_ensemble(mppi_handle_t h, const float* tables_host /* [n_member
 int mppi_set_mlp_member(mppi_handle_t h, int e, const float* table_host, int n_floats, void* stream);
 int mppi_set_mlp_nominal(mppi_handle_t h, int e);
 int mppi_get_mlp_ensemble(mppi_handle_t h, int* n_members_out, int* nominal_out);
+/* Tracking costs for the learned-dynamics models (all five MPPI_MODEL_MLP* ids): a goal that moves along the horizon and state
+ * components that are angles.  The reference is a table rows[n_rows][2 * DS] (DS = 4 or 8, the model's state width): row t is
+ * the goal g_t[DS] and then the weights q_t[DS] of horizon step t; a component the network does not have is padded with g = 0,
+ * q = 0.  The angular mask has bit m set when state component m is an angle.  The cost, in fp32 and in this order (at option
+ * "math" = 0 every operation rounds on its own; the fast levels may contract a * b + c):
+ *     g_t, q_t = row t of the reference                 (no reference: g_t = g, q_t = q of the parameters, as before)
+ *     d[m] = s[m] - g_t[m]
+ *     m angular:  k = rint(d[m] * INV_TWO_PI);  d[m] = d[m] - TWO_PI * k
+ *                 (TWO_PI = 6.2831855f, INV_TWO_PI = 0.15915494f, rint = round half to even: the error lies in [-pi, pi])
+ *     c = 0; for m ascending: c = c + q_t[m] * (d[m] * d[m]); for k ascending: c = c + r[k] * (u[k] * u[k])
+ * The stage cost of step t reads row t; the terminal cost reads row T - 1 with u = 0, the rule of every time-indexed cost here
+ * (the reference solver evaluates it with the stale info["t"] = T - 1): there is no row T.  To weight the END of the horizon,
+ * put the weight into q of row T - 1: it counts for the state of step T - 1 and for the final state.  r stays a parameter.
+ * Every kernel that evaluates the model carries both: the rollout (regenerated noise and tiles, with or without the
+ * control-cost term), the single cooperative launch, the particle rollout (all particles and members share the reference) and
+ * the wavefront-per-trajectory comparison kernel.
+ * Without a reference and without a mask nothing changes: g and q travel in the kernel arguments as before.
+ * The reference rides in the handle's first map slot: a learned-dynamics handle has no maps, and mppi_upload_map /
+ * mppi_build_obstacle_map / mppi_build_lane_map return MPPI_E_INVALID on one (they were accepted and ignored before).
+ *   mppi_set_mlp_reference  the handle keeps its own device copy.  A host table (on_device = 0) is checked (every value
+ *                        finite, else MPPI_E_INVALID), staged and copied on `stream` without a host wait, as mppi_set_discs does
+ *                        it; a device table (on_device = 1) is copied device-to-device in stream order and never meets the
+ *                        host.  rows = NULL or n_rows = 0 switches the reference off.  A buffer too small for the table is
+ *                        reallocated (blocking: set-up path).  A solve with 0 < n_rows < T returns MPPI_E_STATE before
+ *                        anything is launched.
+ *   mppi_get_mlp_reference  n_rows (0: none) and, unless `out` is NULL, the table [n_rows][2 * DS] (a host `out` waits for
+ *                        `stream`).
+ *   mppi_set_mlp_angular / mppi_get_mlp_angular  the mask; MPPI_E_INVALID for a bit at or above DS.  May be set before or after
+ *                        the weight table: the architecture flags and the mask are composed by one owner.
+ * MPPI_E_INVALID on another model's handle.  mppi_clone_state carries the table and the mask; mppi_model_step is dynamics only. */
+int mppi_set_mlp_reference(mppi_handle_t h, const float* rows /* [n_rows][2 * DS] */, int n_rows, int on_device, void* stream);
+int mppi_get_mlp_reference(mppi_handle_t h, float* out, int* n_rows_out, int on_device, void* stream);
+int mppi_set_mlp_angular(mppi_handle_t h, uint32_t mask);
+int mppi_get_mlp_angular(mppi_handle_t h, uint32_t* mask_out);
 /* Moving obstacles for MPPI_MODEL_NAV2D_DISCS (dynamics, parameters and maps of MPPI_MODEL_NAV2D): the predicted discs as a
  * table with one row per horizon step, discs [rows][n][4] = {cx, cy, r2, w}: centre, SQUARED radius (formed by the caller)
  * and penalty of disc j at step t; rows >= T, 0 <= n <= MPPI_MAX_DISCS.  Stage cost of step t, on the state (x, y, .) the

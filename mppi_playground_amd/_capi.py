@@ -55,6 +55,7 @@ SYMBOLS = [
     "mppi_set_mlp_ensemble", "mppi_set_mlp_member", "mppi_set_mlp_nominal", "mppi_get_mlp_ensemble",
     "mppi_set_particle_members", "mppi_get_particle_members",
     "mppi_essps_get_state", "mppi_essps_set_state",
+    "mppi_set_mlp_reference", "mppi_get_mlp_reference", "mppi_set_mlp_angular", "mppi_get_mlp_angular",
 ]
 
 
@@ -74,8 +75,10 @@ class MppiError(RuntimeError):
 _lib = None
 
 
-def load():
-    """dlopen the in-tree extension; raises (never falls back) when it is absent."""
+def load(allow_missing=()):
+    """dlopen the in-tree extension; raises (never falls back) when it is absent.  Every symbol of the header must be there;
+    `allow_missing` names the ones a caller that loads an OLDER build on purpose (an A/B script, before anything else loads
+    the library) will not call: they are left out of the check, and calling one raises AttributeError."""
     global _lib
     if _lib is not None:
         return _lib
@@ -195,7 +198,13 @@ def load():
     lib.mppi_get_particle_members.argtypes = [vp, vp, vp]
     lib.mppi_essps_get_state.argtypes = [vp, vp, vp]
     lib.mppi_essps_set_state.argtypes = [vp, vp, i64]
+    for name, types in (("mppi_set_mlp_reference", [vp, vp, i32, i32, vp]), ("mppi_get_mlp_reference", [vp, vp, vp, i32, vp]),
+                        ("mppi_set_mlp_angular", [vp, u32]), ("mppi_get_mlp_angular", [vp, vp])):
+        if not (name in allow_missing and not hasattr(lib, name)):
+            getattr(lib, name).argtypes = types
     for name in SYMBOLS:
+        if name in allow_missing and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError if the .so does not export what the header declares
         if name not in ("mppi_version", "mppi_last_error"):
             fn.restype = C.c_int

@@ -345,7 +345,19 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
         if (dm.mlp.n != sm.mlp.n) HIP_TRY(dst, dm.mlp.alloc(sm.mlp.n));
         CLONE(model.mlp);
         dm.mlp_members = sm.mlp_members; dm.mlp_nominal = sm.mlp_nominal;
-        dm.ctx.ref = dm.mlp.p + (sm.ctx.ref - sm.mlp.p); dm.ctx.ref_rows = sm.ctx.ref_rows;
+        dm.ctx.ref = dm.mlp.p + (sm.ctx.ref - sm.mlp.p);
+    }
+    if (is_mlp(src->cfg.model)) {  // the tracking reference and the two halves of the flags word (set before or after the weights)
+        dm.mlp_arch = sm.mlp_arch; dm.mlp_angular = sm.mlp_angular;
+        publish_mlp_flags(dst);
+        dm.mlp_ref_rows = 0;
+        if (sm.mlp_ref_rows > 0) {
+            const size_t floats = (size_t)sm.mlp_ref_rows * 2 * (size_t)src->ds;
+            if (dm.mlp_ref.n < floats) HIP_TRY(dst, dm.mlp_ref.alloc(floats));
+            if (int rc = clone_buf(dst, dm.mlp_ref.p, sm.mlp_ref.p, floats)) return rc;
+            dm.mlp_ref_rows = sm.mlp_ref_rows;
+        }
+        publish_mlp_reference(dst);
     }
     if (sm.center_n) {
         HIP_TRY(dst, dm.center8.alloc(sm.center8.n));

@@ -38,6 +38,7 @@ void refresh_pad(mppi_handle_t h, hipStream_t s) {
 // (re)allocate the grid of `slot` and fill in its geometry
 int prepare_map(mppi_handle_t h, int slot, int nx, int ny, float cell, float ox, float oy) {
     if (!h || slot < 0 || slot > 1 || nx < 1 || ny < 1 || !(cell > 0.0f)) return fail(h, MPPI_E_INVALID, "bad map");
+    if (is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "a learned-dynamics handle has no maps");  // (maps[0] carries its reference)
     const size_t n = (size_t)nx * ny;
     if (h->model.map_cells[slot].n < n) HIP_TRY(h, h->model.map_cells[slot].alloc(n));
     MapView& m = h->model.ctx.maps[slot];
@@ -121,6 +122,17 @@ void apply_disc_softness(mppi_handle_t h, float reach, float skirt) {
     const double kappa = (double)reach * (double)reach, phi = (double)skirt;
     h->model.soft_reach = reach; h->model.soft_skirt = skirt;
     set_disc_soft(h->model.ctx, h->cfg.model, (float)(phi * kappa / (kappa - 1.0)), (float)(phi / (kappa - 1.0)));
+}
+
+// The flags word of a learned-dynamics handle (ctx.ref_rows) has this one writer: the architecture flags of the weight table
+// and the angular mask are kept apart on the handle and composed here, so mppi_set_mlp / mppi_set_mlp_ensemble and
+// mppi_set_mlp_angular may come in either order.
+void publish_mlp_flags(mppi_handle_t h) { h->model.ctx.ref_rows = mlp_flags_word(h->model.mlp_arch, h->model.mlp_angular); }
+void publish_mlp_reference(mppi_handle_t h) {
+    set_mlp_reference(h->model.ctx, h->model.mlp_ref_rows > 0 ? h->model.mlp_ref.p : nullptr);
+}
+static int mlp_arch_flags(int hidden_layers, int activation, int residual) {
+    return (hidden_layers == 2 ? MLP_TWO_LAYERS : 0) | (activation == MPPI_MLP_TANH ? MLP_TANH : 0) | (residual ? MLP_RESIDUAL : 0);
 }
 
 }  // namespace mppi
@@ -271,8 +283,8 @@ int mppi_set_mlp(mppi_handle_t h, const float* table, int n_floats, int hidden_l
     HIP_TRY(h, hipMemcpyAsync(h->model.mlp, st, sizeof(float) * (size_t)n_floats, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(ev, s));
     h->model.ctx.ref = h->model.mlp;
-    h->model.ctx.ref_rows = (hidden_layers == 2 ? MLP_TWO_LAYERS : 0) | (activation == MPPI_MLP_TANH ? MLP_TANH : 0) |
-                            (residual ? MLP_RESIDUAL : 0);
+    h->model.mlp_arch = mlp_arch_flags(hidden_layers, activation, residual);
+    publish_mlp_flags(h);
     h->model.mlp_members = 1; h->model.mlp_nominal = 0;  // (an ensemble of one, in the front of whatever the buffer holds)
     return MPPI_OK;
 }
@@ -312,8 +324,8 @@ int mppi_set_mlp_ensemble(mppi_handle_t h, const float* tables, int n_members, i
         if (int rc = upload_mlp_member(h, e, tables + (size_t)e * (size_t)n_floats, n_floats, s)) return rc;
     h->model.mlp_members = n_members; h->model.mlp_nominal = nominal;
     h->model.ctx.ref = h->model.mlp.p + (size_t)nominal * (size_t)n_floats;
-    h->model.ctx.ref_rows = (hidden_layers == 2 ? MLP_TWO_LAYERS : 0) | (activation == MPPI_MLP_TANH ? MLP_TANH : 0) |
-                            (residual ? MLP_RESIDUAL : 0);
+    h->model.mlp_arch = mlp_arch_flags(hidden_layers, activation, residual);
+    publish_mlp_flags(h);
     return MPPI_OK;
 }
 
@@ -347,6 +359,70 @@ int mppi_get_mlp_ensemble(mppi_handle_t h, int* n_members_out, int* nominal_out)
     if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the weight tables belong to the learned-dynamics models");
     if (n_members_out) *n_members_out = h->model.ctx.ref ? h->model.mlp_members : 0;
     if (nominal_out) *nominal_out = h->model.mlp_nominal;
+    return MPPI_OK;
+}
+
+int mppi_set_mlp_reference(mppi_handle_t h, const float* rows, int n_rows, int on_device, void* stream) {
+    if (!h) return MPPI_E_INVALID;
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the tracking reference belongs to the learned-dynamics models");
+    if (n_rows < 0) return fail(h, MPPI_E_INVALID, "tracking reference: n_rows >= 0");
+    auto& m = h->model;
+    if (!rows || n_rows == 0) {  // off: the cost reads goal and q from the parameters again
+        m.mlp_ref_rows = 0;
+        publish_mlp_reference(h);
+        return MPPI_OK;
+    }
+    const size_t floats = (size_t)n_rows * 2 * (size_t)h->ds;
+    if (!on_device)
+        for (size_t i = 0; i < floats; ++i)
+            if (!std::isfinite(rows[i])) return fail(h, MPPI_E_INVALID, "tracking reference: every value must be finite");
+    hipStream_t s = (hipStream_t)stream;
+    if (m.mlp_ref.n < floats) {  // (blocking: earlier launches may still read the old buffer)
+        HIP_TRY(h, hipDeviceSynchronize());
+        m.mlp_ref_rows = 0;
+        publish_mlp_reference(h);
+        HIP_TRY(h, m.mlp_ref.alloc(floats));
+    }
+    if (on_device) {
+        HIP_TRY(h, hipMemcpyAsync(m.mlp_ref, rows, sizeof(float) * floats, hipMemcpyDeviceToDevice, s));
+    } else {
+        float* st = nullptr; hipEvent_t ev = nullptr;
+        if (int rc = stage_slot(h, floats, &st, &ev)) return rc;
+        std::memcpy(st, rows, sizeof(float) * floats);
+        HIP_TRY(h, hipMemcpyAsync(m.mlp_ref, st, sizeof(float) * floats, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipEventRecord(ev, s));
+    }
+    m.mlp_ref_rows = n_rows;
+    publish_mlp_reference(h);
+    return MPPI_OK;
+}
+
+int mppi_get_mlp_reference(mppi_handle_t h, float* out, int* n_rows_out, int on_device, void* stream) {
+    if (!h) return MPPI_E_INVALID;
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the tracking reference belongs to the learned-dynamics models");
+    const int n_rows = h->model.mlp_ref_rows;
+    if (n_rows_out) *n_rows_out = n_rows;
+    if (!out || n_rows == 0) return MPPI_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipMemcpyAsync(out, h->model.mlp_ref, sizeof(float) * (size_t)n_rows * 2 * (size_t)h->ds,
+                              on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    if (!on_device) HIP_TRY(h, hipStreamSynchronize(s));
+    return MPPI_OK;
+}
+
+int mppi_set_mlp_angular(mppi_handle_t h, uint32_t mask) {
+    if (!h) return MPPI_E_INVALID;
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the angular mask belongs to the learned-dynamics models");
+    if (mask >> h->ds) return fail(h, MPPI_E_INVALID, "angular mask: a bit at or above the model's state width");
+    h->model.mlp_angular = mask;
+    publish_mlp_flags(h);
+    return MPPI_OK;
+}
+
+int mppi_get_mlp_angular(mppi_handle_t h, uint32_t* mask_out) {
+    if (!h) return MPPI_E_INVALID;
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the angular mask belongs to the learned-dynamics models");
+    if (mask_out) *mask_out = h->model.mlp_angular;
     return MPPI_OK;
 }
 

@@ -85,7 +85,10 @@ int rollout_particles(mppi_handle_t h, hipStream_t s) {
     do {                                                                                              \
         const size_t shmem = sizeof(float) * RolloutLds::floats(h->d.R, h->d.T, h->d.row, ModelT<MODEL, FASTV>::KROW, false); \
         constexpr bool UCV = FASTV != 0;  /* the FAST kernels exist in the u_in_bounds form only (see use_fast) */ \
-        tm.launch(gen ? rollout_particles_kernel<MODEL, FASTV, true, UCV> : rollout_particles_kernel<MODEL, FASTV, false, UCV>, \
+        constexpr bool TRK = mlp_track(MODEL);  /* (the learned models' instantiations with the tracking cost: mppi_models.hpp) */ \
+        tm.launch(TRK && mlp_tracking(ctx)                                                            \
+                      ? (gen ? rollout_particles_kernel<MODEL, FASTV, true, UCV, TRK> : rollout_particles_kernel<MODEL, FASTV, false, UCV, TRK>) \
+                      : (gen ? rollout_particles_kernel<MODEL, FASTV, true, UCV> : rollout_particles_kernel<MODEL, FASTV, false, UCV>), \
                   grid, dim3(BLOCK), shmem, (const float4*)h->core.noise.p, (const float*)h->core.mean.p,                    \
                   (const float*)p.table.p, h->core.x0_cur, p.costs.p, h->core.mean_used.p, h->core.x0_used.p, h->d,         \
                   h->core.gen, ctx);                                                                  \

@@ -236,15 +236,17 @@ static int solve_fused(mppi_handle_t h, float lambda, float* action_out, float* 
         /* the blocks synchronise through cells in HBM: every one of them must be resident at once.  Checked against the   \
            kernel's own occupancy (cached per (math level, LDS size)); what OTHER work holds of the GPU at run time is what  \
            the polls' time-out is for */                                                                                   \
-        const uint64_t okey = ((uint64_t)(FASTV + 1) << 48) | (uint64_t)shmem;                                             \
+        const bool track = mlp_track(MODEL) && mlp_tracking(h->model.ctx);  /* (the learned models: mppi_models.hpp) */          \
+        const uint64_t okey = ((uint64_t)(FASTV + 1) << 48) | ((uint64_t)track << 47) | (uint64_t)shmem;                  \
+        const auto kern = track ? solve_fused_kernel<MODEL, FASTV, mlp_track(MODEL)> : solve_fused_kernel<MODEL, FASTV, false>; \
         if (h->fused.occ_key != okey) {                                                                                    \
             int nb = 0;                                                                                                    \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, solve_fused_kernel<MODEL, FASTV>, FUSED_BLOCK, shmem) != hipSuccess) nb = 0; \
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, FUSED_BLOCK, shmem) != hipSuccess) nb = 0;          \
             h->fused.occ_key = okey; h->fused.occ_blocks = nb;                                                             \
         }                                                                                                                  \
         if ((int64_t)grid > (int64_t)h->fused.occ_blocks * h->cu_count) { *declined = true; break; }                       \
         StageTimer tm(h, 1, s);  /* (after the occupancy check: a declined launch leaves no empty event pair behind) */    \
-        tm.launch(solve_fused_kernel<MODEL, FASTV>, dim3(grid), dim3(FUSED_BLOCK), shmem, A, h->d, h->core.gen, h->model.ctx, sg, fx);  \
+        tm.launch(kern, dim3(grid), dim3(FUSED_BLOCK), shmem, A, h->d, h->core.gen, h->model.ctx, sg, fx);  \
     } while (0)
     MPPI_DISPATCH(h, CALL_FUSED);
 #undef CALL_FUSED
@@ -319,7 +321,8 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
 #define CALL_WAVE(MODEL, FASTV)                                                                       \
         do {                                                                                          \
             const size_t shw = sizeof(float) * WaveRolloutLds::floats(h->d.R, h->d.T, ModelT<MODEL, FASTV>::DS);          \
-            tmw.launch(rollout_cost_wave_kernel<MODEL, FASTV>, dim3(wgrid), dim3(BLOCK), shw, h->core.noise_std,      \
+            tmw.launch(mlp_track(MODEL) && mlp_tracking(h->model.ctx) ? rollout_cost_wave_kernel<MODEL, FASTV, mlp_track(MODEL)>      \
+                                                                      : rollout_cost_wave_kernel<MODEL, FASTV, false>, dim3(wgrid), dim3(BLOCK), shw, h->core.noise_std,      \
                        h->core.mean, h->core.x0_cur, h->core.costs, mkw.accumulate, mkw.reset_next, h->d, h->model.ctx); \
         } while (0)
         MPPI_DISPATCH(h, CALL_WAVE);
@@ -346,7 +349,15 @@ int mppi_rollout_cost(mppi_handle_t h, void* stream) {
     do {                                                                                              \
         const size_t shmem = sizeof(float) * RolloutLds::floats(h->d.R, h->d.T, h->d.row, ModelT<MODEL, FASTV>::KROW, term); \
         constexpr bool UCV = FASTV != 0;  /* the FAST kernels exist in the u_in_bounds form only (see use_fast) */ \
-        if (term)                                                                                     \
+        constexpr bool TRK = mlp_track(MODEL);  /* (the learned models' instantiations with the tracking cost: mppi_models.hpp) */ \
+        if (TRK && mlp_tracking(h->model.ctx)) {                                                      \
+            if (term)                                                                                 \
+                tm.launch(gen ? rollout_action_cost_kernel<MODEL, FASTV, true, UCV, TRK> : rollout_action_cost_kernel<MODEL, FASTV, false, UCV, TRK>, \
+                          dim3(grid), dim3(BLOCK), shmem, ROLLOUT_ARGS, aca);                         \
+            else                                                                                      \
+                tm.launch(gen ? rollout_cost_kernel<MODEL, FASTV, true, UCV, TRK> : rollout_cost_kernel<MODEL, FASTV, false, UCV, TRK>, \
+                          dim3(grid), dim3(BLOCK), shmem, ROLLOUT_ARGS);                              \
+        } else if (term)                                                                              \
             tm.launch(gen ? rollout_action_cost_kernel<MODEL, FASTV, true, UCV> : rollout_action_cost_kernel<MODEL, FASTV, false, UCV>, \
                       dim3(grid), dim3(BLOCK), shmem, ROLLOUT_ARGS, aca);                             \
         else                                                                                          \

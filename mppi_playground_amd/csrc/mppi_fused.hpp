@@ -199,7 +199,7 @@ __device__ __noinline__ void fused_scalar_step(int rule, int r, int rounds, bool
     }
 }
 
-template <int MODEL, int FAST>
+template <int MODEL, int FAST, bool TRACK = false>
 __global__ __launch_bounds__(FUSED_BLOCK) void solve_fused_kernel(FusedArgs A, Dims d, GenCtx gen, ModelCtx ctx,
                                                                   SgFilter sg, FusedCtx fx) {
     using M = ModelT<MODEL, FAST>;
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(FUSED_BLOCK) void solve_fused_kernel(FusedArgs A, D
         const uint64_t gi = (uint64_t)(d.sample_offset + i);
         const bool inherit = (d.sample_offset + i) < d.inherit_count;
         const float4* mp = inherit ? s_mean4 : s_mean4 + d.R;
-        total = lane_cost<MODEL, FAST, true, UC>(nullptr, gi, gen, mp, s_ktab, s_x0, d, ctx);
+        total = lane_cost<MODEL, FAST, true, UC, false, TRACK>(nullptr, gi, gen, mp, s_ktab, s_x0, d, ctx);
         A.costs[i] = total;
     }
     FX_TRACE(1);

@@ -319,6 +319,13 @@ struct MppiSolver {
         DevBuf<float> mlp;             // weight tables of the learned-dynamics models [mlp_members][mlp_table_floats(ds, dc)] (mppi_set_mlp:
                                        // one; mppi_set_mlp_ensemble); ctx.ref points at member mlp_nominal's
         int mlp_members = 0, mlp_nominal = 0;
+        // tracking costs of the learned-dynamics models (mppi_set_mlp_reference / mppi_set_mlp_angular; mppi_models.hpp says where
+        // they ride in ctx): the handle's own copy of the reference table [mlp_ref_rows][2 * ds] (0 rows: no reference), and the
+        // two halves of the flags word ctx.ref_rows, which publish_mlp_flags alone composes
+        DevBuf<float> mlp_ref;
+        int mlp_ref_rows = 0;
+        int mlp_arch = 0;              // MLP_TWO_LAYERS | MLP_TANH | MLP_RESIDUAL as mppi_set_mlp / mppi_set_mlp_ensemble gave them
+        uint32_t mlp_angular = 0;      // bit m: state component m is an angle (mppi_set_mlp_angular)
         // device-resident reference window (mppi_set_center_path / mppi_ref_window)
         DevBuf<float> center8;         // [n][8] centre line with sin/cos of the yaw
         DevBuf<int32_t> win_dind;      // [rows] index offsets of the window rows
@@ -549,6 +556,8 @@ inline int check_ready(mppi_handle_t h) {
         return fail(h, MPPI_E_STATE, "obstacle map (slot 0) not uploaded");
     if (is_racing_model(m) && !h->model.map_cells[1]) return fail(h, MPPI_E_STATE, "lane map (slot 1) not uploaded");
     if (is_mlp(m) && !h->model.ctx.ref) return fail(h, MPPI_E_STATE, "no weight table: call mppi_set_mlp or mppi_set_mlp_ensemble first");
+    if (is_mlp(m) && h->model.mlp_ref_rows > 0 && h->model.mlp_ref_rows < h->d.T)
+        return fail(h, MPPI_E_STATE, "tracking reference has fewer rows than the horizon");
     // the step table (mppi_models.hpp): every part its layout has covers the horizon (ctx.ref is aimed at it once they do)
     const StepLayout L = step_layout(m);
     if (L.has_ref() && h->model.ref_part_rows < h->d.T)
@@ -601,6 +610,8 @@ int prepare_map(mppi_handle_t h, int slot, int nx, int ny, float cell, float ox,
 int reserve_step_table(mppi_handle_t h, int rows);
 void publish_step_table(mppi_handle_t h);
 void apply_disc_softness(mppi_handle_t h, float reach, float skirt);
+void publish_mlp_flags(mppi_handle_t h);      // ctx.ref_rows of a learned-dynamics handle from mlp_arch and mlp_angular
+void publish_mlp_reference(mppi_handle_t h);  // aims the reference slot of ctx at mlp_ref (null while mlp_ref_rows == 0)
 
 // the per-column sigma table the sampler reads (see MppiSolver::Cov)
 inline float* sigma_table(mppi_handle_t h) { return h->wide ? h->core.coltab.p : h->cov.sigtab.p; }

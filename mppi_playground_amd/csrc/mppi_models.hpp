@@ -83,6 +83,35 @@ MPPI_HD const int32_t __attribute__((address_space(4)))* member_offsets(const Mo
 #else
 MPPI_HD const int32_t* member_offsets(const ModelCtx& c) { return reinterpret_cast<const int32_t*>(c.pad); }
 #endif
+// Tracking costs (mppi_set_mlp_reference, mppi_set_mlp_angular): the reference table [rows][2 * DS] — row t is the goal g_t[DS]
+// and then the weights q_t[DS] of horizon step t — rides in one more field these models leave free, ModelCtx::maps[0].cells,
+// and the mask of the angular state components in bits 8-15 of ModelCtx::ref_rows, beside the three architecture flags.  All
+// zeros is "off", on the host and on the device alike: a null pointer means no reference, and goal and q come from P[] as
+// before — the kernel arguments, held in scalar registers across the horizon loop as they always were; a default solver runs
+// the loop it ran.  With a reference the row is read through the constant address space: where the step index is wave-uniform
+// (every lane-per-trajectory kernel) the 2 * DS values are one scalar load per step, where it differs per lane
+// (rollout_cost_wave_kernel) the same source compiles to per-lane loads.  mlp_flags_word composes ref_rows: its one writer on
+// the host is publish_mlp_flags (capi_model.hip).
+// The kernels that evaluate these models exist twice: TRACK = false is the kernel as it was (MlpModel::cost_plain: g, q of P[],
+// nothing of the above in it), TRACK = true carries the tracking cost (MlpModel::cost); mlp_tracking(ctx) at the launch site
+// picks one, and mlp_track(MODEL) is the template argument to ask for (false for every other model: no second instantiation).
+// In the TRACK kernels the table pointer costs two scalar registers across a horizon loop that has none to spare
+// (profiles/r26_mlp_tracking.md): they are won back there — no look-ahead step constant (trajectory_cost), and the
+// end-of-kernel `threadIdx.x == 0` formed from the `lane == 0` mask (mppi_rollout_kernel.inc).
+constexpr bool mlp_track(int model) { return is_mlp(model); }
+constexpr int MLP_ARCH_MASK = MLP_TWO_LAYERS | MLP_TANH | MLP_RESIDUAL, MLP_ANGULAR_SHIFT = 8;
+constexpr int32_t mlp_flags_word(int arch, uint32_t angular) { return (int32_t)((uint32_t)(arch & MLP_ARCH_MASK) | ((angular & 0xffu) << MLP_ANGULAR_SHIFT)); }
+MPPI_HD uint32_t mlp_angular(const ModelCtx& c) { return ((uint32_t)c.ref_rows >> MLP_ANGULAR_SHIFT) & 0xffu; }
+#if defined(__HIP_DEVICE_COMPILE__)
+MPPI_HD const float __attribute__((address_space(4)))* mlp_reference(const ModelCtx& c) {
+    return (const float __attribute__((address_space(4)))*)c.maps[0].cells;
+}
+#else
+MPPI_HD const float* mlp_reference(const ModelCtx& c) { return reinterpret_cast<const float*>(c.maps[0].cells); }
+#endif
+MPPI_HD bool mlp_tracking(const ModelCtx& c) { return c.maps[0].cells != nullptr || mlp_angular(c) != 0; }  // (launch-uniform)
+inline void set_mlp_reference(ModelCtx& c, const float* table) { c.maps[0].cells = reinterpret_cast<const uint8_t*>(table); }
+constexpr float MLP_TWO_PI = 6.2831855f, MLP_INV_TWO_PI = 0.15915494f;  // the wrap of an angular error: d - TWO_PI * rint(d * INV_TWO_PI)
 
 // The step table: the models whose cost reads step-constant values carry ONE table with one row per horizon step.  It is
 // ModelCtx::ref, ref_rows is the number of rows every part of it covers (the solve checks it against the horizon), and the

@@ -702,9 +702,11 @@ typedef const float* MlpTable;
 
 template <int DSN, int DCN, bool FAST>
 struct MlpModel {
-    using K = NoStepConst;
+    // The step constant is the step index itself: cost() forms the address of its reference row from it (mppi_models.hpp:
+    // mlp_reference).  Nothing is staged in LDS (KROW = 0): the row is 2 * DS scalar operands where t is wave-uniform.
+    struct K { int t; };
     static constexpr int KROW = 0;
-    static MPPI_HD K load_k(const float*, int) { return K{}; }
+    static MPPI_HD K load_k(const float*, int t) { return K{t}; }
     static MPPI_HD void check_state(const ModelCtx&, const float*, bool&) {}
     static MPPI_HD void enter(float*) {}
     static constexpr int DS = DSN, DC = DCN, IN = DS + DC, H = MPPI_MLP_HIDDEN;
@@ -762,7 +764,55 @@ struct MlpModel {
                           : (DS == 8 && PG == MPPI_MP8_G && PQ == MPPI_MP8_Q && PR == MPPI_MP8_R),
                   "the parameter layout of include/mppi_hip.h");
     static_assert(PR + DC <= MPPI_MAX_PARAMS && OB3 + DS == mlp_table_floats(DS, DC), "parameters and table as the host sizes them");
-    static MPPI_HD float cost(const ModelCtx& c, const K&, const float* s, const float* u, const float*, bool&) {
+    // Stage cost of step k.t (the terminal cost: the caller hands row T - 1 and u = 0).  Goal and weights are row k.t of the
+    // reference table, or P[] when there is none (the only P[] slots that path reads: g, q, r as before); the error of an
+    // angular component is wrapped into [-pi, pi] by d - TWO_PI * rint(d * INV_TWO_PI), each operation rounded on its own in
+    // mppi::strict.  Both choices are launch-uniform branches: a handle without a mask executes no wrap instruction.
+    static MPPI_HD float cost(const ModelCtx& c, const K& k, const float* s, const float* u, const float*, bool&) {
+        const float* P = c.P;
+        const MlpTable R = mlp_reference(c);
+        uint32_t ang = mlp_angular(c);
+#if defined(__HIP_DEVICE_COMPILE__)
+        // (opaque per call: otherwise the DS tests `ang & (1 << m)` are hoisted out of the horizon loop as DS 64-bit lane masks held
+        // across it — 8 or 16 SGPRs: every 8-state kernel spilled scalar registers into vector lanes.  Formed per step they are
+        // transient.)
+        asm volatile("" : "+s"(ang));
+#endif
+        float g[DS], q[DS];
+        if (R) {
+            const MlpTable row = R + k.t * (2 * DS);
+#pragma unroll
+            for (int m = 0; m < DS; ++m) { g[m] = row[m]; q[m] = row[DS + m]; }
+        } else {
+#pragma unroll
+            for (int m = 0; m < DS; ++m) { g[m] = P[PG + m]; q[m] = P[PQ + m]; }
+        }
+        float a = 0.0f;
+        if (ang) {
+#pragma unroll
+            for (int m = 0; m < DS; ++m) {
+                float d = s[m] - g[m];
+                if (ang & (1u << m)) {
+                    const float turns = rintf(d * MLP_INV_TWO_PI);
+                    d = d - MLP_TWO_PI * turns;
+                }
+                a = a + q[m] * (d * d);
+            }
+        } else {
+#pragma unroll
+            for (int m = 0; m < DS; ++m) {
+                const float d = s[m] - g[m];
+                a = a + q[m] * (d * d);
+            }
+        }
+#pragma unroll
+        for (int k2 = 0; k2 < DC; ++k2) a = a + P[PR + k2] * (u[k2] * u[k2]);
+        return a;
+    }
+    // The cost of a handle with neither reference nor mask, as it always was: every kernel that evaluates these models exists
+    // in two instantiations (TRACK, mppi_rollout.hpp) and the launch site picks one (mlp_tracking), so a default solver runs the
+    // kernel it ran, with no pointer, no step index and no branch in its loop.
+    static MPPI_HD float cost_plain(const ModelCtx& c, const K&, const float* s, const float* u, const float*, bool&) {
         const float* P = c.P;
         float a = 0.0f;
 #pragma unroll
@@ -771,7 +821,7 @@ struct MlpModel {
             a = a + P[PQ + m] * (d * d);
         }
 #pragma unroll
-        for (int k = 0; k < DC; ++k) a = a + P[PR + k] * (u[k] * u[k]);
+        for (int k2 = 0; k2 < DC; ++k2) a = a + P[PR + k2] * (u[k2] * u[k2]);
         return a;
     }
 };

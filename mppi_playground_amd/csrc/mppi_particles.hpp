@@ -21,7 +21,7 @@ namespace mppi {
 // carry particle m through ensemble member members[m] (mppi_set_particle_members): the launch site hands the members'
 // offsets into the weight buffer in ctx.pad (mppi_models.hpp: member_offsets), the block reads its entry at a uniform address
 // and moves ITS copy of ctx.ref.  The cost of (i, m) is then what a plain handle holding that member's table computes.
-template <int MODEL, int FAST, bool GEN, bool UC>
+template <int MODEL, int FAST, bool GEN, bool UC, bool TRACK = false>
 __global__ __launch_bounds__(BLOCK) void rollout_particles_kernel(const float4* __restrict__ noise,
                                                                   const float* __restrict__ mean,
                                                                   const float* __restrict__ particles,
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(BLOCK) void rollout_particles_kernel(const float4* 
         // the constant address space: scalar loads, as before).  No map: ctx.pad is null and the pointer stays where it was.
         ModelCtx mctx = ctx;
         if (ctx.pad != nullptr) mctx.ref = ctx.ref + member_offsets(ctx)[m];
-        const float total = lane_cost<MODEL, FAST, GEN, UC>(np, gi, gen, mp, s_ktab, particles + m * M::DS, d, mctx);
+        const float total = lane_cost<MODEL, FAST, GEN, UC, false, TRACK>(np, gi, gen, mp, s_ktab, particles + m * M::DS, d, mctx);
         if (i < d.N) s_out[i] = total;
     } else {
         const float total = lane_cost<MODEL, FAST, GEN, UC>(np, gi, gen, mp, s_ktab, particles + m * M::DS, d, ctx);

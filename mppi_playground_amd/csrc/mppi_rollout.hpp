@@ -67,7 +67,12 @@ __device__ __forceinline__ void rollout_trace_loop(unsigned entry_lo) {
 // (mppi.py:313) — read one group at a time where its steps run (no look-ahead: four VGPRs instead of eight); the lane
 // accumulates A = sum g * U over its solver-clamped actions and adds kappa * A behind the cost sum.  `kappa` waits in LDS
 // (see rollout_cost_kernel on what SGPRs held across the loop cost).  Off: no code, `g4` and `kappa` are null.
-template <int MODEL, int FAST, bool GEN, bool UC, bool VAR = false, bool X0OUT = false, bool AC = false>
+// TRACK (the learned models only; every kernel that walks them carries it as its last template argument): the instantiation
+// with the tracking cost (reference table, angular mask: MlpModel::cost).  TRACK = false is the kernel of a handle with
+// neither, compiled from the text it was compiled from before the tracking cost existed (MlpModel::cost_plain; same
+// registers, same code): the launch sites pick one per launch (mlp_tracking), so the choice is made outside the horizon loop
+// and a default solver runs the kernel it ran.
+template <int MODEL, int FAST, bool GEN, bool UC, bool VAR = false, bool X0OUT = false, bool AC = false, bool TRACK = false>
 __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, uint64_t gi, const GenCtx& gen,
                                                  const float4* mean4, const float* ktab,
                                                  const float* __restrict__ x0, const Dims& d, const ModelCtx& ctx_in,
@@ -119,8 +124,10 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
     int t = 0;
     float A = 0.0f;  // (AC) sum over (t, k) of g * U, sequential fp32
     auto one_step = [&](const float* ev, const float* mv, const float* gv) {
-        const K kcur = knext;
-        knext = M::load_k(ktab, min(t + 1, d.T - 1));
+        // (with the tracking cost the learned models' step constant is the step index itself: no look-ahead to keep in a register)
+        K kcur = knext;
+        if constexpr (is_mlp(MODEL) && TRACK) kcur = M::load_k(ktab, t);
+        else knext = M::load_k(ktab, min(t + 1, d.T - 1));
         float u[DC];
 #pragma unroll
         for (int k = 0; k < DC; ++k) u[k] = clampf(mv[k] + ev[k], lo[k], hi[k]);
@@ -131,7 +138,8 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
         float sn[DS], ss[DS];
         if constexpr (is_racing_model(MODEL)) M::step(ctx, s, u, sn, ss, bad, UC, FAST != 0, VAR);
         else M::step(ctx, s, u, sn, ss, bad, UC, FAST != 0);
-        if constexpr (X0OUT) acc.add(M::cost(ctx, kcur, ss, u, pu, bad, t == 0));
+        if constexpr (is_mlp(MODEL) && !TRACK) acc.add(M::cost_plain(ctx, kcur, ss, u, pu, bad));
+        else if constexpr (X0OUT) acc.add(M::cost(ctx, kcur, ss, u, pu, bad, t == 0));
         else acc.add(M::cost(ctx, kcur, ss, u, pu, bad));
 #pragma unroll
         for (int k = 0; k < DC; ++k) { pl[k] = pu[k]; pu[k] = u[k]; }
@@ -242,7 +250,10 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
             e1 = *nptr;
         }
     }
-    if (t < d.T) {  // last group: ragged (T*dc not a multiple of 4), or, behind the regenerating loop, the complete last one
+    // (One step per group, dc = 4, and no last group held back: the loops above have walked all T steps and nothing is left.  Said
+    // at compile time: the compiler proved it for the 4-control learned model only while that model's step constant did not
+    // carry the step index, and the dead third copy of the step cost its library-math kernels 16 VGPRs and a wave per SIMD.)
+    if ((SPG > 1 || LAST_GROUP_IN_EPILOGUE || !(is_mlp(MODEL) && TRACK)) && t < d.T) {  // last group: ragged (T*dc not a multiple of 4), or, behind the regenerating loop, the complete last one
         const float ev[4] = {e.x, e.y, e.z, e.w};
         const float mv[4] = {m4.x, m4.y, m4.z, m4.w};
         float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -263,7 +274,10 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
     float zero[DC];
 #pragma unroll
     for (int k = 0; k < DC; ++k) zero[k] = 0.0f;
-    const float term = M::cost(ctx, knext, s, zero, pl, bad);
+    if constexpr (is_mlp(MODEL) && TRACK) knext = M::load_k(ktab, d.T - 1);
+    float term;
+    if constexpr (is_mlp(MODEL) && !TRACK) term = M::cost_plain(ctx, knext, s, zero, pl, bad);
+    else term = M::cost(ctx, knext, s, zero, pl, bad);
     if constexpr (AC) return action_cost_total(acc.total(term), *kappa, A);
     else return acc.total(term);
 }
@@ -274,7 +288,7 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
 // (EntryGeneral) and carry no redo: inlining the library-math walk next to the hot loop cost the racing kernel 18 VGPRs,
 // two waves per SIMD and 3.6 % of its time (profiles/r04_experiments.md).
 // AC: every copy carries the control-cost term (the redo computes its own A from scratch, like its cost sum).
-template <int MODEL, int FAST, bool GEN, bool UC, bool AC = false>
+template <int MODEL, int FAST, bool GEN, bool UC, bool AC = false, bool TRACK = false>
 __device__ __forceinline__ float lane_cost(const float4* __restrict__ np, uint64_t gi, const GenCtx& gen, const float4* mp,
                                            const float* s_ktab, const float* __restrict__ x0, const Dims& d,
                                            const ModelCtx& ctx, const float4* g4 = nullptr, const float* kappa = nullptr) {
@@ -289,11 +303,11 @@ __device__ __forceinline__ float lane_cost(const float4* __restrict__ np, uint64
     if (is_racing_model(MODEL) && FAST != 0 && ctx.unit_L)
         total = trajectory_cost<MODEL, FAST, GEN, UC, true, false, AC>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa);
     else
-        total = trajectory_cost<MODEL, FAST, GEN, UC, false, false, AC>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa);
+        total = trajectory_cost<MODEL, FAST, GEN, UC, false, false, AC, TRACK>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa);
     if constexpr (FAST != 0 && !EntryGeneral<M>::value) {
         if (bad) {  // a fast path left its validity range: redo this lane with the library math
             bool ignore = false;
-            total = trajectory_cost<MODEL, 0, GEN, false, false, false, AC>(np, gi, gen, mp, s_ktab, x0, d, ctx, ignore, g4, kappa);
+            total = trajectory_cost<MODEL, 0, GEN, false, false, false, AC, TRACK>(np, gi, gen, mp, s_ktab, x0, d, ctx, ignore, g4, kappa);
         }
     }
     return total;
@@ -337,7 +351,7 @@ struct ActionCostArgs {
 // cost) and a wavefront shuffle reduction sums them.  Same model functors, same results up to the
 // summation order of the T+1 stage costs.  Measured 20x slower than the lane-per-trajectory mapping
 //  because the recurrence runs on 1/64 of the machine.
-template <int MODEL, int FAST>
+template <int MODEL, int FAST, bool TRACK = false>
 __global__ __launch_bounds__(BLOCK) void rollout_cost_wave_kernel(const float* __restrict__ eps_std,
                                                                   const float* __restrict__ mean,
                                                                   const float* __restrict__ x0,
@@ -393,7 +407,8 @@ __global__ __launch_bounds__(BLOCK) void rollout_cost_wave_kernel(const float* _
 #pragma unroll
             for (int k = 0; k < DC; ++k) { u[k] = term ? 0.0f : sU[t * DC + k]; pu[k] = sU[tp * DC + k]; }
             const K kk = M::load_k(ctx.ref, term ? d.T - 1 : t);
-            part += M::cost(ctx, kk, st, u, pu, bad);
+            if constexpr (is_mlp(MODEL) && !TRACK) part += M::cost_plain(ctx, kk, st, u, pu, bad);
+            else part += M::cost(ctx, kk, st, u, pu, bad);
         }
         const float total = wave_sum(part);
         if (lane == 0) { costs[i] = total; wmin = fminf(wmin, total); }

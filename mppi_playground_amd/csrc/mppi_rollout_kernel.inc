@@ -2,7 +2,7 @@
 // (MPPI_ROLLOUT_AC 0) and, with the opt-in control-cost term (mppi_action_cost.hpp), as rollout_action_cost_kernel
 // (MPPI_ROLLOUT_AC 1: one more launch argument, 4R more floats of LDS for g).  One text, so that the kernel without the
 // term is compiled from exactly what it was compiled from before the term existed: same name, arguments and registers.
-template <int MODEL, int FAST, bool GEN, bool UC>
+template <int MODEL, int FAST, bool GEN, bool UC, bool TRACK = false>
 __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void MPPI_ROLLOUT_KERNEL(const float4* __restrict__ noise,
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ x0,
@@ -97,9 +97,9 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void MPPI_ROLLOUT_KERNEL(c
         bool bad = false;
         const float4* mp = inherit ? s_mean4 : s_mean4 + d.R;  // (RolloutLds::zeros, in float4 groups)
 #if MPPI_ROLLOUT_AC
-        total = lane_cost<MODEL, FAST, GEN, UC, true>(np, gi, gen, mp, s_ktab, x0, d, ctx, s_mean4 + 2 * d.R /* RolloutLds::g, in float4 groups */, &s_kappa);
+        total = lane_cost<MODEL, FAST, GEN, UC, true, TRACK>(np, gi, gen, mp, s_ktab, x0, d, ctx, s_mean4 + 2 * d.R /* RolloutLds::g, in float4 groups */, &s_kappa);
 #else
-        total = lane_cost<MODEL, FAST, GEN, UC>(np, gi, gen, mp, s_ktab, x0, d, ctx);
+        total = lane_cost<MODEL, FAST, GEN, UC, false, TRACK>(np, gi, gen, mp, s_ktab, x0, d, ctx);
 #endif
         if (i < d.N) s_costs[i] = total;
         else total = INFINITY;
@@ -108,7 +108,14 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void MPPI_ROLLOUT_KERNEL(c
     if (lane == 0) s_min[wid] = wm;
     __syncthreads();
     ROLLOUT_TRACE(4);
-    if (threadIdx.x == 0) {
+    // (The learned models' instantiations with the tracking cost form this test anew: the compiler otherwise keeps the lane mask of the `threadIdx.x == 0` at the top of
+    // the kernel in a scalar register pair across the horizon loop (here: from the mask of `lane == 0`, which is held anyway, and the
+    // wave's index as a scalar), and their loop has none to spare — mlp84's library-math tile
+    // kernel spilled the pair into a vector lane, 80 -> 81 VGPRs and six waves per SIMD -> five, and mlp41's library-math
+    // control-cost kernel 96 -> 97 and five -> four.  Every other model: the text it was.)
+    bool first_thread = threadIdx.x == 0;
+    if constexpr (is_mlp(MODEL) && TRACK) first_thread = lane == 0 && __builtin_amdgcn_readfirstlane(wid) == 0;
+    if (first_thread) {
         float m = s_min[0];
 #pragma unroll
         for (int w = 1; w < BLOCK / WAVE; ++w) m = fminf(m, s_min[w]);

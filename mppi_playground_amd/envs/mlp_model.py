@@ -1,4 +1,4 @@
-"""Learned dynamics as an MPPI plugin: a small multi-layer perceptron fitted to data, with a quadratic cost.
+"""Learned dynamics as an MPPI plugin: a small multi-layer perceptron fitted to data, with a quadratic tracking cost.
 
     model = MLPModel.from_module(net, goal=[...], q=[...], r=[...])      # net: nn.Sequential of Linear / ReLU / Tanh
     solver = MPPI(dim_state=4, dim_control=dc, dynamics=model.dynamics, cost_func=model.cost, ...)
@@ -22,6 +22,15 @@ The arithmetic, in fp32 and in this order (the torch code below, the device func
     o[m] = b3[m]; for j ascending: o[m] = o[m] + W3[m][j] * h[j]
     next[m] = s[m] + o[m] if residual else o[m]
     cost = sum_m q[m] * (s[m] - goal[m])^2 + sum_k r[k] * u[k]^2      (terminal: the same with u = 0)
+
+Tracking (include/mppi_hip.h: mppi_set_mlp_reference has the contract): `set_reference(goals, q)` gives every horizon step a
+goal (and weights) of its own — the stage cost of step t reads row t = info["t"], the terminal cost row T-1 (the reference
+solver's stale info["t"]: there is no row T; to weight the end of the horizon put the weight into q of row T-1, it counts for
+the state of step T-1 and for the final state) — and `angular=[...]` names the state components that are angles: their error
+is wrapped into [-pi, pi],
+    d = s[m] - g_t[m];  k = rint(d * INV_TWO_PI);  d = d - TWO_PI * k        (TWO_PI = float32 6.2831855, INV_TWO_PI = 0.15915494)
+so a heading needs no (cos, sin) encoding.  The reference is ONE padded float32 table [rows, 2 * DS] (row: g_t then q_t),
+updated in place while its shape stays the same, so a captured graph of the callables (graph_callables=True) stays valid.
 """
 from __future__ import annotations
 
@@ -33,6 +42,8 @@ import torch
 from pi_mpc.native import native_model
 
 HIDDEN = 32  # hidden width of the device table (MPPI_MLP_HIDDEN)
+TWO_PI = float(np.float32(6.2831855))       # the wrap of an angular error, as the device spells it (float32 values)
+INV_TWO_PI = float(np.float32(0.15915494))
 
 
 def _f32(a) -> np.ndarray:
@@ -50,10 +61,10 @@ class MLPModel:
     CONTROLS = (1, 2)   # control widths they are compiled for
 
     def __init__(self, weights: Sequence, biases: Sequence, activation: str = "tanh", residual: bool = True, goal=None,
-                 q=None, r=None):
+                 q=None, r=None, angular=None):
         """weights / biases: per layer, torch.nn.Linear's layout — W1 [h1, ds + dc], (W2 [h2, h1],) W3 [ds, h] with
         ds <= 4 state components, dc = 1 or 2 controls and h1, h2 <= 32.  goal, q: [ds] (defaults 0 / 1), r: [dc] (default 0).
-        ValueError for anything the device path does not take."""
+        angular: indices (< ds) of the state components that are angles.  ValueError for anything the device path does not take."""
         if activation not in ("relu", "tanh"):
             raise ValueError("activation must be 'relu' or 'tanh'")
         self.activation = activation
@@ -75,6 +86,77 @@ class MLPModel:
         self.goal, self.q, self.r = goal4, q4, vec(r, dc, 0.0, "r")
         for a in (self.goal, self.q, self.r):
             a.flags.writeable = False
+        self.set_angular(angular)
+        self._ref = None            # the reference table [rows, 2 * DS] (float32, wherever set_reference was given it), or None
+        self._ref_own_q = False     # its q half was given (False: it mirrors self.q)
+        self._ref_mirrors = {}      # (device, dtype) -> the copy the callables read there, kept in step IN PLACE
+        self.reference_version = 0
+
+    def set_angular(self, angular) -> None:
+        """Which state components are angles: indices below the network's own state width, or None / () for none.  For the
+        callables and the device alike, from the next solve on.  ValueError for an index out of range, a repeated index or a
+        non-integer."""
+        ds = self.dim_state_model
+        idx = [] if angular is None else list(angular)
+        if any(isinstance(i, (bool, np.bool_)) or not isinstance(i, (int, np.integer)) for i in idx):
+            raise ValueError("angular: integer indices of state components")
+        if any(not 0 <= int(i) < ds for i in idx) or len({int(i) for i in idx}) != len(idx):
+            raise ValueError(f"angular: distinct indices in 0..{ds - 1} (the network's own state width)")
+        self.angular = tuple(sorted(int(i) for i in idx))  # (read it; change it through set_angular)
+
+    @property
+    def angular_mask(self) -> int:
+        """Bit m is set when state component m is an angle (mppi_set_mlp_angular)."""
+        return sum(1 << m for m in self.angular)
+
+    @property
+    def reference(self):
+        """The reference table, float32 [rows, 2 * DS] (row t: the goal of step t, then its weights), or None.  It may be
+        rewritten in place (a device tensor: on the device); call reference_changed() afterwards."""
+        return self._ref
+
+    def set_reference(self, goals, q=None) -> None:
+        """A goal per horizon step: goals [rows, ds] (a host array, a host tensor or a device tensor; the solver needs
+        rows >= horizon), q [rows, ds] or None — with None every row carries the model's own q as it stands at the solve (a
+        later set_cost(q=...) shows in those rows).  set_reference(None) switches the reference off.  While the shape and the
+        device stay the same the table is updated IN PLACE (a captured graph of the callables stays valid).  ValueError for a
+        wrong width, non-finite values or a q of another shape."""
+        if goals is None:
+            self._ref, self._ref_own_q, self._ref_mirrors = None, False, {}
+            self.reference_version += 1
+            return
+        ds, DS = self.dim_state_model, self.DS
+
+        def tensor(v, name):
+            t = v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float32))
+            t = t.to(torch.float32)
+            if t.ndim != 2 or t.shape[1] != ds or t.shape[0] < 1:
+                raise ValueError(f"{name} must be [rows, {ds}] (got {list(t.shape)})")
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError(f"{name} must be finite")
+            return t
+
+        g = tensor(goals, "goals")
+        qq = None if q is None else tensor(q, "q").to(g.device)
+        if qq is not None and qq.shape != g.shape:
+            raise ValueError(f"q must have the shape of goals {list(g.shape)} (got {list(qq.shape)})")
+        tab = torch.zeros(g.shape[0], 2 * DS, dtype=torch.float32, device=g.device)
+        tab[:, :ds] = g
+        tab[:, DS:DS + ds] = qq if qq is not None else torch.as_tensor(np.array(self.q[:ds]), device=g.device)
+        self._ref_own_q = qq is not None
+        if self._ref is not None and self._ref.shape == tab.shape and self._ref.device == tab.device:
+            self._ref.copy_(tab)
+        else:
+            self._ref, self._ref_mirrors = tab, {}
+        self.reference_changed()
+
+    def reference_changed(self) -> None:
+        """Tell the callables and the solver that the reference table was rewritten in place."""
+        if self._ref is not None:
+            for t in self._ref_mirrors.values():
+                if t is not self._ref:
+                    t.copy_(self._ref)
+        self.reference_version += 1
 
     def set_cost(self, goal=None, q=None, r=None) -> None:
         """Replace cost parameters (same shapes as the constructor's; None keeps one) for the callables and the device alike."""
@@ -90,6 +172,9 @@ class MLPModel:
             full.flags.writeable = False
             setattr(self, name, full)
         self._torch = {}
+        if q is not None and self._ref is not None and not self._ref_own_q:  # rows without weights of their own follow q
+            self._ref[:, self.DS:self.DS + ds] = torch.as_tensor(np.array(self.q[:ds]), device=self._ref.device)
+            self.reference_changed()
 
     # ------------------------------------------------------------------ weights
     def _set(self, weights, biases) -> None:
@@ -175,7 +260,8 @@ class MLPModel:
     def native_inputs(self) -> dict:
         return {"params": [float(v) for v in np.concatenate([self.goal, self.q, self.r])],
                 "mlp": {"table": self.table, "hidden_layers": self.hidden_layers, "activation": self.activation,
-                        "residual": self.residual, "version": self.version}}
+                        "residual": self.residual, "version": self.version, "angular": self.angular_mask,
+                        "reference": self._ref, "reference_version": self.reference_version}}
 
     # ------------------------------------------------------------------ the callables
     def _on(self, ref: torch.Tensor):
@@ -184,6 +270,17 @@ class MLPModel:
         if got is None:
             got = tuple(torch.tensor(np.array(a)).to(ref.device, ref.dtype) for a in self.layers + (self.goal, self.q, self.r))
             self._torch[key] = got
+        return got
+
+    def _ref_on(self, ref: torch.Tensor):
+        """The reference table where and as `ref` lives (one tensor per place, kept in step in place), or None."""
+        if self._ref is None:
+            return None
+        key = (ref.device, ref.dtype)
+        got = self._ref_mirrors.get(key)
+        if got is None:
+            got = self._ref if (self._ref.device, self._ref.dtype) == key else self._ref.to(ref.device, ref.dtype)
+            self._ref_mirrors[key] = got
         return got
 
     def _act(self, z: torch.Tensor) -> torch.Tensor:
@@ -210,9 +307,15 @@ class MLPModel:
     @native_model(lambda owner: owner.model_name, "cost", _provider)
     def cost(self, state: torch.Tensor, action: torch.Tensor, info=None) -> torch.Tensor:
         goal, q, r = self._on(state)[6:]
+        tab = self._ref_on(state)
+        if tab is not None:  # the goal and the weights of this step: row info["t"] (the terminal call carries T - 1)
+            row = tab[0 if info is None else info["t"]]
+            goal, q = row[:self.DS], row[self.DS:]
         c = torch.zeros(state.shape[0], device=state.device, dtype=state.dtype)
         for m in range(self.DS):
             d = state[:, m] - goal[m]
+            if m in self.angular:
+                d = d - TWO_PI * torch.round(d * INV_TWO_PI)
             c = c + q[m] * (d * d)
         for k in range(self.dim_control):
             c = c + r[k] * (action[:, k] * action[:, k])
@@ -222,8 +325,9 @@ class MLPModel:
         new = object.__new__(type(self))
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            new.__dict__[k] = {} if k == "_torch" else (tuple(a.copy() for a in v) if k == "layers" else
-                                                        v.copy() if isinstance(v, np.ndarray) else v)
+            new.__dict__[k] = {} if k in ("_torch", "_ref_mirrors") else (tuple(a.copy() for a in v) if k == "layers" else
+                                                                          v.copy() if isinstance(v, np.ndarray) else
+                                                                          v.clone() if torch.is_tensor(v) else v)
         for a in (new.goal, new.q, new.r):
             a.flags.writeable = False
         return new
@@ -259,7 +363,7 @@ class MLPEnsemble:
         if any(type(m) is not type(first) for m in members[1:]):
             raise ValueError("the members of an ensemble are of one class: all MLPModel or all MLPModel8")
         for m in members[1:]:
-            for name in ("dim_state_model", "dim_control", "hidden_layers", "activation", "residual"):
+            for name in ("dim_state_model", "dim_control", "hidden_layers", "activation", "residual", "angular"):
                 if getattr(m, name) != getattr(first, name):
                     raise ValueError(f"the members of an ensemble share one architecture: {name} differs "
                                      f"({getattr(m, name)!r} against {getattr(first, name)!r})")
@@ -310,6 +414,35 @@ class MLPEnsemble:
         for m in self._members:
             m.set_cost(goal=goal, q=q, r=r)
 
+    def set_reference(self, goals, q=None) -> None:
+        """MLPModel.set_reference for every member: there is one cost, and ONE table — the members share the tensor (and its
+        copies on other devices), so rewriting `reference` in place and reference_changed() reach every member."""
+        first = self._members[0]
+        first.set_reference(goals, q)
+        self._share_reference()
+
+    def _share_reference(self) -> None:
+        first = self._members[0]
+        for m in self._members[1:]:
+            m._ref, m._ref_own_q, m._ref_mirrors = first._ref, first._ref_own_q, first._ref_mirrors
+            m.reference_version = max(m.reference_version, first.reference_version) + 1
+
+    def set_angular(self, angular) -> None:
+        """MLPModel.set_angular for every member (checked on the first: a refused mask changes none)."""
+        self._members[0].set_angular(angular)
+        for m in self._members[1:]:
+            m.set_angular(angular)
+
+    def reference_changed(self) -> None:
+        """The shared table was rewritten in place: its copies on other devices are refreshed ONCE, every member's version moves."""
+        first = self._members[0]
+        first.reference_changed()
+        for m in self._members[1:]:
+            if m._ref is first._ref:
+                m.reference_version += 1
+            else:
+                m.reference_changed()
+
     @property
     def version(self) -> int:
         """Moves whenever a member's weights or the nominal index changed."""
@@ -330,7 +463,7 @@ class MLPEnsemble:
 
     def __getattr__(self, name):  # (the architecture, as the members state it)
         if name in ("dim_state_model", "dim_control", "hidden_layers", "activation", "residual", "goal", "q", "r", "DS",
-                    "dim_state", "pad_state"):
+                    "dim_state", "pad_state", "angular", "angular_mask", "reference", "reference_version"):
             return getattr(self.__dict__["_members"][self.__dict__["_nominal"]], name)
         raise AttributeError(name)
 
@@ -356,4 +489,6 @@ class MLPEnsemble:
         memo[id(self)] = new
         new.__dict__.update(_members=[copy.deepcopy(m, memo) for m in self._members], _nominal=self._nominal,
                             _nominal_version=self._nominal_version, _stack=None)
+        if all(m._ref is self._members[0]._ref for m in self._members):  # (one table stays one table in the copy)
+            new._share_reference()
         return new

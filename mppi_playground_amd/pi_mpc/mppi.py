@@ -612,6 +612,16 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                 self._h.call("mppi_set_mlp", tab.ctypes.data_as(C.c_void_p), int(tab.size), int(mlp["hidden_layers"]),
                              _capi.MLP_ACTIVATIONS[mlp["activation"]], int(bool(mlp["residual"])), self._stream())
                 self._h.mlp_key = key
+        if mlp is not None:  # the tracking cost: the angular mask and the reference table, each when its owner moved it
+            mask = int(mlp.get("angular", 0))
+            if getattr(self._h, "mlp_angular_key", 0) != mask:  # (a new handle starts without a mask)
+                self._h.call("mppi_set_mlp_angular", mask)
+                self._h.mlp_angular_key = mask
+            table = mlp.get("reference")
+            key = None if table is None else (id(self._cost_owner), id(table), mlp["reference_version"])
+            if getattr(self._h, "mlp_reference_key", None) != key:  # (kept on the handle: a new one starts without a reference)
+                self._put_mlp_reference(table)
+                self._h.mlp_reference_key = key
         discs = spec.get("discs")
         if discs is not None:  # moving discs: the predicted table travels again whenever its owner bumped the version
             key = (id(self._cost_owner), discs["version"])
@@ -654,6 +664,26 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             if nominal != held[2]:
                 h.call("mppi_set_mlp_nominal", nominal)
         h.mlp_members = (id(self._cost_owner), versions, nominal)
+
+    def _put_mlp_reference(self, table) -> None:
+        """An MLPModel's reference table [rows, 2 * DS] -> the handle (mppi_set_mlp_reference, on the current stream, no host
+        wait): a tensor on the solver's device is copied there, anything else goes through the pinned staging ring; None
+        switches the reference off.  ValueError for a table shorter than the horizon."""
+        if table is None:
+            self._h.call("mppi_set_mlp_reference", None, 0, 0, self._stream())
+            return
+        shape = tuple(table.shape)
+        if len(shape) != 2 or shape[1] != 2 * self._dim_state:
+            raise ValueError(f"reference table: expected [rows, {2 * self._dim_state}], got {list(shape)}")
+        if shape[0] < self._horizon:
+            raise ValueError(f"reference table: {shape[0]} rows for a horizon of {self._horizon} (one row per step)")
+        if torch.is_tensor(table) and table.is_cuda and table.device == self._device:
+            dev = table.detach().to(torch.float32).contiguous()
+            self._h.call("mppi_set_mlp_reference", _ptr(dev), shape[0], 1, self._stream())
+            self._mlp_reference_keep = dev  # (alive until the next table: the copy reads it in stream order)
+        else:
+            host = np.ascontiguousarray(table.detach().cpu().numpy() if torch.is_tensor(table) else table, dtype=np.float32)
+            self._h.call("mppi_set_mlp_reference", host.ctypes.data_as(C.c_void_p), shape[0], 0, self._stream())
 
     def _put_discs(self, table) -> None:
         """The moving-disc table [rows, n, 4] = {cx, cy, r2, w} per horizon step -> the handle (mppi_set_discs, on the
