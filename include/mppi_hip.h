@@ -267,6 +267,30 @@ int mppi_set_mlp_reference(mppi_handle_t h, const float* rows /* [n_rows][2 * DS
 int mppi_get_mlp_reference(mppi_handle_t h, float* out, int* n_rows_out, int on_device, void* stream);
 int mppi_set_mlp_angular(mppi_handle_t h, uint32_t mask);
 int mppi_get_mlp_angular(mppi_handle_t h, uint32_t* mask_out);
+/* A learned terminal value for the learned-dynamics models: a second network V evaluated ONCE per trajectory on its final
+ * state s_T (as the dynamics network produced it: the angular mask does not wrap the value's input) and added behind the
+ * terminal cost.  One float32 table of 32 * DS + 1121 values,
+ *     W1[32][DS], b1[32], W2[32][32], b2[32], w3[32], b3[1]
+ * with unused parts zero (narrower layers; W2 and b2 with one hidden layer).  hidden_layers (1 or 2) and activation
+ * (MPPI_MLP_RELU / MPPI_MLP_TANH) are the value's own, independent of the dynamics network's.  In fp32, every sum in ascending
+ * index order and, at "math" = 0, every a * b + c rounded on its own:
+ *     z1[j] = b1[j] + sum_i W1[j][i] * s[i];  h1 = act(z1)
+ *     z2[j] = b2[j] + sum_i W2[j][i] * h1[i]; h2 = act(z2)          (two hidden layers)
+ *     V = b3 + sum_j w3[j] * h2[j]                                   (one hidden layer: h1[j])
+ *     terminal = quad_T + (weight * V)        quad_T: the terminal cost as it is without a value (row T - 1 of a reference)
+ *     terminal = weight * V                   with replace_terminal = 1
+ * Every kernel that evaluates the model's cost carries it (the same ones as the tracking cost, in the same instantiations); the
+ * batch-1 rollout, the re-rolled trajectories and mppi_model_step compute states only.  Without a value nothing changes.
+ *   mppi_set_mlp_value  table_host = NULL clears the value.  Otherwise checked like mppi_set_mlp (a learned-dynamics handle, the
+ *                        exact count, 1 or 2 layers, a known activation, every value and the weight finite: else
+ *                        MPPI_E_INVALID), staged and copied on `stream` without a host wait.
+ *   mppi_get_mlp_value  the count (0: no value), layers, activation, weight and replace flag, and the table unless `out` is NULL
+ *                        (waits for `stream`).
+ * mppi_clone_state carries the table, the flags and the weight. */
+int mppi_set_mlp_value(mppi_handle_t h, const float* table_host, int n_floats, int hidden_layers, int activation, float weight,
+                       int replace_terminal, void* stream);
+int mppi_get_mlp_value(mppi_handle_t h, float* out, int* n_floats_out, int* hidden_layers_out, int* activation_out,
+                       float* weight_out, int* replace_terminal_out, void* stream);
 /* Moving obstacles for MPPI_MODEL_NAV2D_DISCS (dynamics, parameters and maps of MPPI_MODEL_NAV2D): the predicted discs as a
  * table with one row per horizon step, discs [rows][n][4] = {cx, cy, r2, w}: centre, SQUARED radius (formed by the caller)
  * and penalty of disc j at step t; rows >= T, 0 <= n <= MPPI_MAX_DISCS.  Stage cost of step t, on the state (x, y, .) the

@@ -358,6 +358,15 @@ int mppi_clone_state(mppi_handle_t dst, mppi_handle_t src) {
             dm.mlp_ref_rows = sm.mlp_ref_rows;
         }
         publish_mlp_reference(dst);
+        // the learned terminal value: table, flags and weight
+        dm.mlp_value_set = false;
+        if (sm.mlp_value_set) {
+            if (dm.mlp_value.n < sm.mlp_value.n) HIP_TRY(dst, dm.mlp_value.alloc(sm.mlp_value.n));
+            if (int rc = clone_buf(dst, dm.mlp_value.p, sm.mlp_value.p, sm.mlp_value.n)) return rc;
+            dm.mlp_value_set = true;
+        }
+        dm.mlp_value_flags = sm.mlp_value_flags; dm.mlp_value_weight = sm.mlp_value_weight;
+        publish_mlp_value(dst);
     }
     if (sm.center_n) {
         HIP_TRY(dst, dm.center8.alloc(sm.center8.n));

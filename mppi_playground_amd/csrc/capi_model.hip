@@ -127,9 +127,15 @@ void apply_disc_softness(mppi_handle_t h, float reach, float skirt) {
 // The flags word of a learned-dynamics handle (ctx.ref_rows) has this one writer: the architecture flags of the weight table
 // and the angular mask are kept apart on the handle and composed here, so mppi_set_mlp / mppi_set_mlp_ensemble and
 // mppi_set_mlp_angular may come in either order.
-void publish_mlp_flags(mppi_handle_t h) { h->model.ctx.ref_rows = mlp_flags_word(h->model.mlp_arch, h->model.mlp_angular); }
+void publish_mlp_flags(mppi_handle_t h) {
+    h->model.ctx.ref_rows = mlp_flags_word(h->model.mlp_arch, h->model.mlp_angular, h->model.mlp_value_set ? h->model.mlp_value_flags : 0);
+}
 void publish_mlp_reference(mppi_handle_t h) {
     set_mlp_reference(h->model.ctx, h->model.mlp_ref_rows > 0 ? h->model.mlp_ref.p : nullptr);
+}
+void publish_mlp_value(mppi_handle_t h) {
+    set_mlp_value(h->model.ctx, h->model.mlp_value_set ? h->model.mlp_value.p : nullptr, h->model.mlp_value_weight);
+    publish_mlp_flags(h);
 }
 static int mlp_arch_flags(int hidden_layers, int activation, int residual) {
     return (hidden_layers == 2 ? MLP_TWO_LAYERS : 0) | (activation == MPPI_MLP_TANH ? MLP_TANH : 0) | (residual ? MLP_RESIDUAL : 0);
@@ -423,6 +429,56 @@ int mppi_get_mlp_angular(mppi_handle_t h, uint32_t* mask_out) {
     if (!h) return MPPI_E_INVALID;
     if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the angular mask belongs to the learned-dynamics models");
     if (mask_out) *mask_out = h->model.mlp_angular;
+    return MPPI_OK;
+}
+
+int mppi_set_mlp_value(mppi_handle_t h, const float* table, int n_floats, int hidden_layers, int activation, float weight,
+                       int replace_terminal, void* stream) {
+    if (!h) return MPPI_E_INVALID;
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the terminal value belongs to the learned-dynamics models");
+    auto& m = h->model;
+    if (!table) {  // off: the terminal cost is the quadratic again
+        m.mlp_value_set = false; m.mlp_value_flags = 0; m.mlp_value_weight = 0.0f;
+        publish_mlp_value(h);
+        return MPPI_OK;
+    }
+    if (n_floats != mlp_value_floats(h->ds)) return fail(h, MPPI_E_INVALID, "value table: wrong number of values for this model");
+    if (hidden_layers < 1 || hidden_layers > 2 || (activation != MPPI_MLP_RELU && activation != MPPI_MLP_TANH) ||
+        (replace_terminal != 0 && replace_terminal != 1))
+        return fail(h, MPPI_E_INVALID, "value table: hidden_layers 1 or 2, activation relu or tanh, replace_terminal 0 or 1");
+    if (!std::isfinite(weight)) return fail(h, MPPI_E_INVALID, "value table: the weight must be finite");
+    for (int i = 0; i < n_floats; ++i)
+        if (!std::isfinite(table[i])) return fail(h, MPPI_E_INVALID, "value table: every value must be finite");
+    hipStream_t s = (hipStream_t)stream;
+    if (!m.mlp_value) HIP_TRY(h, m.mlp_value.alloc((size_t)n_floats));
+    float* st = nullptr; hipEvent_t ev = nullptr;
+    if (int rc = stage_slot(h, (size_t)n_floats, &st, &ev)) return rc;
+    std::memcpy(st, table, sizeof(float) * (size_t)n_floats);
+    HIP_TRY(h, hipMemcpyAsync(m.mlp_value, st, sizeof(float) * (size_t)n_floats, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(ev, s));
+    m.mlp_value_set = true;
+    m.mlp_value_flags = (hidden_layers == 2 ? MLP_VALUE_TWO_LAYERS : 0) | (activation == MPPI_MLP_TANH ? MLP_VALUE_TANH : 0) |
+                        (replace_terminal ? MLP_VALUE_REPLACE : 0);
+    m.mlp_value_weight = weight;
+    publish_mlp_value(h);
+    return MPPI_OK;
+}
+
+int mppi_get_mlp_value(mppi_handle_t h, float* out, int* n_floats_out, int* hidden_layers_out, int* activation_out,
+                       float* weight_out, int* replace_terminal_out, void* stream) {
+    if (!h) return MPPI_E_INVALID;
+    if (!is_mlp(h->cfg.model)) return fail(h, MPPI_E_INVALID, "the terminal value belongs to the learned-dynamics models");
+    const auto& m = h->model;
+    const int n = m.mlp_value_set ? mlp_value_floats(h->ds) : 0;
+    if (n_floats_out) *n_floats_out = n;
+    if (hidden_layers_out) *hidden_layers_out = n == 0 ? 0 : (m.mlp_value_flags & MLP_VALUE_TWO_LAYERS) ? 2 : 1;
+    if (activation_out) *activation_out = (m.mlp_value_flags & MLP_VALUE_TANH) ? MPPI_MLP_TANH : MPPI_MLP_RELU;
+    if (weight_out) *weight_out = m.mlp_value_weight;
+    if (replace_terminal_out) *replace_terminal_out = (m.mlp_value_flags & MLP_VALUE_REPLACE) ? 1 : 0;
+    if (!out || n == 0) return MPPI_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipMemcpyAsync(out, m.mlp_value, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
     return MPPI_OK;
 }
 

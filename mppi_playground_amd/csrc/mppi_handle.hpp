@@ -326,6 +326,12 @@ struct MppiSolver {
         int mlp_ref_rows = 0;
         int mlp_arch = 0;              // MLP_TWO_LAYERS | MLP_TANH | MLP_RESIDUAL as mppi_set_mlp / mppi_set_mlp_ensemble gave them
         uint32_t mlp_angular = 0;      // bit m: state component m is an angle (mppi_set_mlp_angular)
+        // the learned terminal value (mppi_set_mlp_value): its table [mlp_value_floats(ds)], whether one is set, its flags
+        // (MLP_VALUE_*: the third part of the flags word) and its weight; publish_mlp_value aims ctx at it
+        DevBuf<float> mlp_value;
+        bool mlp_value_set = false;
+        int mlp_value_flags = 0;
+        float mlp_value_weight = 0.0f;
         // device-resident reference window (mppi_set_center_path / mppi_ref_window)
         DevBuf<float> center8;         // [n][8] centre line with sin/cos of the yaw
         DevBuf<int32_t> win_dind;      // [rows] index offsets of the window rows
@@ -612,6 +618,7 @@ void publish_step_table(mppi_handle_t h);
 void apply_disc_softness(mppi_handle_t h, float reach, float skirt);
 void publish_mlp_flags(mppi_handle_t h);      // ctx.ref_rows of a learned-dynamics handle from mlp_arch and mlp_angular
 void publish_mlp_reference(mppi_handle_t h);  // aims the reference slot of ctx at mlp_ref (null while mlp_ref_rows == 0)
+void publish_mlp_value(mppi_handle_t h);      // aims the value slot of ctx at mlp_value with its weight (null while none is set)
 
 // the per-column sigma table the sampler reads (see MppiSolver::Cov)
 inline float* sigma_table(mppi_handle_t h) { return h->wide ? h->core.coltab.p : h->cov.sigtab.p; }

@@ -98,9 +98,31 @@ MPPI_HD const int32_t* member_offsets(const ModelCtx& c) { return reinterpret_ca
 // In the TRACK kernels the table pointer costs two scalar registers across a horizon loop that has none to spare
 // (profiles/r26_mlp_tracking.md): they are won back there — no look-ahead step constant (trajectory_cost), and the
 // end-of-kernel `threadIdx.x == 0` formed from the `lane == 0` mask (mppi_rollout_kernel.inc).
+// A learned terminal value (mppi_set_mlp_value): a second, smaller network V(s_T) evaluated once per trajectory on its final
+// state and added to (or put in place of) the terminal cost.  Its table — W1[H][DS], b1[H], W2[H][H], b2[H], w3[H], b3[1],
+// unused parts zero — rides in ModelCtx::maps[1].cells, its weight in ModelCtx::maps[1].cell (a float these models leave free)
+// and its three flags in bits 16-18 of ModelCtx::ref_rows.  A null pointer means no value.  It lives in the TRACK kernels only,
+// behind a launch-uniform branch outside the horizon loop (trajectory_cost; lane T of rollout_cost_wave_kernel).
 constexpr bool mlp_track(int model) { return is_mlp(model); }
-constexpr int MLP_ARCH_MASK = MLP_TWO_LAYERS | MLP_TANH | MLP_RESIDUAL, MLP_ANGULAR_SHIFT = 8;
-constexpr int32_t mlp_flags_word(int arch, uint32_t angular) { return (int32_t)((uint32_t)(arch & MLP_ARCH_MASK) | ((angular & 0xffu) << MLP_ANGULAR_SHIFT)); }
+constexpr int MLP_ARCH_MASK = MLP_TWO_LAYERS | MLP_TANH | MLP_RESIDUAL, MLP_ANGULAR_SHIFT = 8, MLP_VALUE_SHIFT = 16;
+constexpr int MLP_VALUE_TWO_LAYERS = 1, MLP_VALUE_TANH = 2, MLP_VALUE_REPLACE = 4, MLP_VALUE_MASK = 7;  // (as shifted down)
+constexpr int mlp_value_floats(int ds) {
+    return MPPI_MLP_HIDDEN * ds + MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN * MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN + MPPI_MLP_HIDDEN + 1;
+}
+constexpr int32_t mlp_flags_word(int arch, uint32_t angular, int value = 0) {
+    return (int32_t)((uint32_t)(arch & MLP_ARCH_MASK) | ((angular & 0xffu) << MLP_ANGULAR_SHIFT) |
+                     ((uint32_t)(value & MLP_VALUE_MASK) << MLP_VALUE_SHIFT));
+}
+MPPI_HD int mlp_value_flags(const ModelCtx& c) { return (int)(((uint32_t)c.ref_rows >> MLP_VALUE_SHIFT) & (uint32_t)MLP_VALUE_MASK); }
+MPPI_HD bool mlp_value_on(const ModelCtx& c) { return c.maps[1].cells != nullptr; }  // (launch-uniform)
+MPPI_HD float mlp_value_weight(const ModelCtx& c) { return c.maps[1].cell; }
+// A block's LDS copy of the value's pointer and weight: the rollout kernels park the two there across the horizon loop, which
+// has no scalar registers to spare for them (mppi_rollout_kernel.inc), and trajectory_cost reads them back behind the loop.
+struct MlpValueSlot { const float* table; float weight; int64_t n; };  // (n: the kernel's sample count, which waits there too)
+inline void set_mlp_value(ModelCtx& c, const float* table, float weight) {
+    c.maps[1].cells = reinterpret_cast<const uint8_t*>(table);
+    c.maps[1].cell = table ? weight : 0.0f;
+}
 MPPI_HD uint32_t mlp_angular(const ModelCtx& c) { return ((uint32_t)c.ref_rows >> MLP_ANGULAR_SHIFT) & 0xffu; }
 #if defined(__HIP_DEVICE_COMPILE__)
 MPPI_HD const float __attribute__((address_space(4)))* mlp_reference(const ModelCtx& c) {
@@ -109,7 +131,9 @@ MPPI_HD const float __attribute__((address_space(4)))* mlp_reference(const Model
 #else
 MPPI_HD const float* mlp_reference(const ModelCtx& c) { return reinterpret_cast<const float*>(c.maps[0].cells); }
 #endif
-MPPI_HD bool mlp_tracking(const ModelCtx& c) { return c.maps[0].cells != nullptr || mlp_angular(c) != 0; }  // (launch-uniform)
+MPPI_HD bool mlp_tracking(const ModelCtx& c) {  // (launch-uniform: a reference, a mask or a terminal value)
+    return c.maps[0].cells != nullptr || mlp_angular(c) != 0 || mlp_value_on(c);
+}
 inline void set_mlp_reference(ModelCtx& c, const float* table) { c.maps[0].cells = reinterpret_cast<const uint8_t*>(table); }
 constexpr float MLP_TWO_PI = 6.2831855f, MLP_INV_TWO_PI = 0.15915494f;  // the wrap of an angular error: d - TWO_PI * rint(d * INV_TWO_PI)
 

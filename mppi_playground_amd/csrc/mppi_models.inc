@@ -809,6 +809,57 @@ struct MlpModel {
         for (int k2 = 0; k2 < DC; ++k2) a = a + P[PR + k2] * (u[k2] * u[k2]);
         return a;
     }
+    // The learned terminal value V(s) of the final state (mppi_models.hpp: set_mlp_value; the TRACK kernels only, once per
+    // trajectory behind the horizon loop).  Offsets into its table: W1[H][DS], b1[H], W2[H][H], b2[H], w3[H], b3[1].  Written
+    // like step(): the weights are scalar operands, layer 1 is unrolled into 32 statically indexed registers — live only here,
+    // where step()'s are dead — and layer 2 is one rolled loop; every sum in ascending index order.  One hidden layer forms V
+    // from h1.  Depth and activation are the value's own flags, not the dynamics network's.
+    static constexpr int VB1 = H * DS, VW2 = VB1 + H, VB2 = VW2 + H * H, VW3 = VB2 + H, VB3 = VW3 + H;
+    static_assert(VB3 + 1 == mlp_value_floats(DS), "the value table as the host sizes it");
+    static MPPI_HD float value(const float* table, int flags, const float* s) {
+        const MlpTable W = (MlpTable)table;
+        const bool use_tanh = (flags & MLP_VALUE_TANH) != 0;
+        float h1[H];
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            float z = W[VB1 + j];
+#pragma unroll
+            for (int i = 0; i < DS; ++i) z = z + W[j * DS + i] * s[i];
+            h1[j] = mlp_act<FAST>(z, use_tanh);
+        }
+        float v = W[VB3];
+        if (flags & MLP_VALUE_TWO_LAYERS) {
+#pragma clang loop unroll(disable)
+            for (int j = 0; j < H; ++j) {
+                const MlpTable w2 = W + VW2 + j * H;
+                float z = W[VB2 + j];
+#pragma unroll
+                for (int i = 0; i < H; ++i) z = z + w2[i] * h1[i];
+                v = v + W[VW3 + j] * mlp_act<FAST>(z, use_tanh);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < H; ++j) v = v + W[VW3 + j] * h1[j];
+        }
+        return v;
+    }
+    static MPPI_HD float value(const ModelCtx& c, const float* s) {
+        return value(reinterpret_cast<const float*>(c.maps[1].cells), mlp_value_flags(c), s);
+    }
+    // The terminal cost with the value in it: quad + (weight * V), or weight * V alone (MLP_VALUE_REPLACE).  `table` and
+    // `weight` are wave-uniform: the context's, or a block's LDS copy of them (MlpValueSlot, mppi_models.hpp).
+    static MPPI_HD float terminal_with_value(const float* table, int flags, float weight, float quad, const float* s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        // (opaque here, like the angular mask in cost(): the tests of the three flags are otherwise formed in front of the horizon
+        // loop and held across it as scalar registers the loop does not have)
+        asm volatile("" : "+s"(flags));
+#endif
+        const float wv = weight * value(table, flags, s);
+        return (flags & MLP_VALUE_REPLACE) ? wv : quad + wv;
+    }
+    static MPPI_HD float terminal_with_value(const ModelCtx& c, float quad, const float* s) {
+        return terminal_with_value(reinterpret_cast<const float*>(c.maps[1].cells), mlp_value_flags(c), mlp_value_weight(c), quad, s);
+    }
     // The cost of a handle with neither reference nor mask, as it always was: every kernel that evaluates these models exists
     // in two instantiations (TRACK, mppi_rollout.hpp) and the launch site picks one (mlp_tracking), so a default solver runs the
     // kernel it ran, with no pointer, no step index and no branch in its loop.

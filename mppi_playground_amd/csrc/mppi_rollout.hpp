@@ -72,11 +72,13 @@ __device__ __forceinline__ void rollout_trace_loop(unsigned entry_lo) {
 // neither, compiled from the text it was compiled from before the tracking cost existed (MlpModel::cost_plain; same
 // registers, same code): the launch sites pick one per launch (mlp_tracking), so the choice is made outside the horizon loop
 // and a default solver runs the kernel it ran.
-template <int MODEL, int FAST, bool GEN, bool UC, bool VAR = false, bool X0OUT = false, bool AC = false, bool TRACK = false>
+template <int MODEL, int FAST, bool GEN, bool UC, bool VAR = false, bool X0OUT = false, bool AC = false, bool TRACK = false,
+          bool SLOT = false>
 __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, uint64_t gi, const GenCtx& gen,
                                                  const float4* mean4, const float* ktab,
                                                  const float* __restrict__ x0, const Dims& d, const ModelCtx& ctx_in,
-                                                 bool& bad, const float4* g4 = nullptr, const float* kappa = nullptr) {
+                                                 bool& bad, const float4* g4 = nullptr, const float* kappa = nullptr,
+                                                 const MlpValueSlot* vslot = nullptr) {
     using M = ModelT<MODEL, FAST>;
     using K = typename M::K;
     constexpr int DS = M::DS, DC = M::DC, SPG = 4 / DC;
@@ -278,6 +280,23 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
     float term;
     if constexpr (is_mlp(MODEL) && !TRACK) term = M::cost_plain(ctx, knext, s, zero, pl, bad);
     else term = M::cost(ctx, knext, s, zero, pl, bad);
+    // The learned terminal value of the final state (mppi_set_mlp_value): launch-uniform, once per trajectory, TRACK only.  Its
+    // pointer and weight come from the context, or — SLOT: the caller has parked them — from the block's LDS copy `vslot`:
+    // read back here as vector values and made scalar again, so that the table is read with scalar loads either way.
+    if constexpr (is_mlp(MODEL) && TRACK) {
+        if constexpr (SLOT) {
+            const volatile MlpValueSlot* slot = vslot;  // (volatile: read back HERE, not carried from the store in scalar registers)
+            const uint64_t p = (uint64_t)slot->table;
+            const uint64_t pu = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)p) |
+                                (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(p >> 32)) << 32;
+            if (pu != 0) {
+                const float w = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)slot->weight)));
+                term = M::terminal_with_value((const float*)pu, mlp_value_flags(ctx), w, term, s);
+            }
+        } else if (mlp_value_on(ctx)) {
+            term = M::terminal_with_value(ctx, term, s);
+        }
+    }
     if constexpr (AC) return action_cost_total(acc.total(term), *kappa, A);
     else return acc.total(term);
 }
@@ -288,10 +307,11 @@ __device__ __forceinline__ float trajectory_cost(const float4* __restrict__ np, 
 // (EntryGeneral) and carry no redo: inlining the library-math walk next to the hot loop cost the racing kernel 18 VGPRs,
 // two waves per SIMD and 3.6 % of its time (profiles/r04_experiments.md).
 // AC: every copy carries the control-cost term (the redo computes its own A from scratch, like its cost sum).
-template <int MODEL, int FAST, bool GEN, bool UC, bool AC = false, bool TRACK = false>
+template <int MODEL, int FAST, bool GEN, bool UC, bool AC = false, bool TRACK = false, bool SLOT = false>
 __device__ __forceinline__ float lane_cost(const float4* __restrict__ np, uint64_t gi, const GenCtx& gen, const float4* mp,
                                            const float* s_ktab, const float* __restrict__ x0, const Dims& d,
-                                           const ModelCtx& ctx, const float4* g4 = nullptr, const float* kappa = nullptr) {
+                                           const ModelCtx& ctx, const float4* g4 = nullptr, const float* kappa = nullptr,
+                                           const MlpValueSlot* vslot = nullptr) {
     using M = ModelT<MODEL, FAST>;
     bool bad = false;
     float total;
@@ -303,11 +323,11 @@ __device__ __forceinline__ float lane_cost(const float4* __restrict__ np, uint64
     if (is_racing_model(MODEL) && FAST != 0 && ctx.unit_L)
         total = trajectory_cost<MODEL, FAST, GEN, UC, true, false, AC>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa);
     else
-        total = trajectory_cost<MODEL, FAST, GEN, UC, false, false, AC, TRACK>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa);
+        total = trajectory_cost<MODEL, FAST, GEN, UC, false, false, AC, TRACK, SLOT>(np, gi, gen, mp, s_ktab, x0, d, ctx, bad, g4, kappa, vslot);
     if constexpr (FAST != 0 && !EntryGeneral<M>::value) {
         if (bad) {  // a fast path left its validity range: redo this lane with the library math
             bool ignore = false;
-            total = trajectory_cost<MODEL, 0, GEN, false, false, false, AC, TRACK>(np, gi, gen, mp, s_ktab, x0, d, ctx, ignore, g4, kappa);
+            total = trajectory_cost<MODEL, 0, GEN, false, false, false, AC, TRACK, SLOT>(np, gi, gen, mp, s_ktab, x0, d, ctx, ignore, g4, kappa, vslot);
         }
     }
     return total;
@@ -407,8 +427,15 @@ __global__ __launch_bounds__(BLOCK) void rollout_cost_wave_kernel(const float* _
 #pragma unroll
             for (int k = 0; k < DC; ++k) { u[k] = term ? 0.0f : sU[t * DC + k]; pu[k] = sU[tp * DC + k]; }
             const K kk = M::load_k(ctx.ref, term ? d.T - 1 : t);
-            if constexpr (is_mlp(MODEL) && !TRACK) part += M::cost_plain(ctx, kk, st, u, pu, bad);
-            else part += M::cost(ctx, kk, st, u, pu, bad);
+            if constexpr (is_mlp(MODEL) && !TRACK) {
+                part += M::cost_plain(ctx, kk, st, u, pu, bad);
+            } else if constexpr (is_mlp(MODEL)) {  // lane T adds the learned terminal value of the final state
+                float c = M::cost(ctx, kk, st, u, pu, bad);
+                if (term && mlp_value_on(ctx)) c = M::terminal_with_value(ctx, c, st);
+                part += c;
+            } else {
+                part += M::cost(ctx, kk, st, u, pu, bad);
+            }
         }
         const float total = wave_sum(part);
         if (lane == 0) { costs[i] = total; wmin = fminf(wmin, total); }

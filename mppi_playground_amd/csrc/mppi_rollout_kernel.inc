@@ -42,6 +42,20 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void MPPI_ROLLOUT_KERNEL(c
         s_min_key = min_key;
         if (stamps != nullptr && blockIdx.x == 0) stamps[0] = wall_clock64();
     }
+    // (The learned models' instantiations with the tracking cost: the pointer and the weight of the terminal value wait for the
+    // end of the horizon loop in LDS as well — three more scalar registers held across it took mlp84's library-math tile kernel
+    // from 80 to 81 VGPRs and six waves per SIMD to five, and mlp41's library-math control-cost kernel from 96 to 97 and five
+    // to four.  Every other instantiation: no slot, no code.)
+    const MlpValueSlot* vslot = nullptr;
+    if constexpr (is_mlp(MODEL) && TRACK) {
+        __shared__ MlpValueSlot s_value;
+        if (threadIdx.x == 0) {
+            s_value.table = reinterpret_cast<const float*>(ctx.maps[1].cells);
+            s_value.weight = ctx.maps[1].cell;
+            s_value.n = d.N;
+        }
+        vslot = &s_value;
+    }
     // RolloutLds: [4*R] mean groups, [4*R] zeros (samples that do not inherit the mean), (with the control-cost term: [4*R] g =
     // mean * inv_covariance,) then [T*KROW] step rows
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
@@ -97,11 +111,13 @@ __global__ __launch_bounds__(BLOCK) MPPI_ROLLOUT_ATTR void MPPI_ROLLOUT_KERNEL(c
         bool bad = false;
         const float4* mp = inherit ? s_mean4 : s_mean4 + d.R;  // (RolloutLds::zeros, in float4 groups)
 #if MPPI_ROLLOUT_AC
-        total = lane_cost<MODEL, FAST, GEN, UC, true, TRACK>(np, gi, gen, mp, s_ktab, x0, d, ctx, s_mean4 + 2 * d.R /* RolloutLds::g, in float4 groups */, &s_kappa);
+        total = lane_cost<MODEL, FAST, GEN, UC, true, TRACK, is_mlp(MODEL) && TRACK>(np, gi, gen, mp, s_ktab, x0, d, ctx, s_mean4 + 2 * d.R /* RolloutLds::g, in float4 groups */, &s_kappa, vslot);
 #else
-        total = lane_cost<MODEL, FAST, GEN, UC, false, TRACK>(np, gi, gen, mp, s_ktab, x0, d, ctx);
+        total = lane_cost<MODEL, FAST, GEN, UC, false, TRACK, is_mlp(MODEL) && TRACK>(np, gi, gen, mp, s_ktab, x0, d, ctx, nullptr, nullptr, vslot);
 #endif
-        if (i < d.N) s_costs[i] = total;
+        int64_t n = d.N;  // (with the slot: read back from it — the sample count is then no scalar pair held across the loop)
+        if constexpr (is_mlp(MODEL) && TRACK) n = static_cast<const volatile MlpValueSlot*>(vslot)->n;
+        if (i < n) s_costs[i] = total;
         else total = INFINITY;
     }
     const float wm = wave_min(total);

@@ -31,6 +31,17 @@ is wrapped into [-pi, pi],
     d = s[m] - g_t[m];  k = rint(d * INV_TWO_PI);  d = d - TWO_PI * k        (TWO_PI = float32 6.2831855, INV_TWO_PI = 0.15915494)
 so a heading needs no (cos, sin) encoding.  The reference is ONE padded float32 table [rows, 2 * DS] (row: g_t then q_t),
 updated in place while its shape stays the same, so a captured graph of the callables (graph_callables=True) stays valid.
+
+A learned terminal value (include/mppi_hip.h: mppi_set_mlp_value has the contract): `set_value(weights, biases)` gives the model
+a second, smaller network V over the state — one or two hidden layers of at most 32 units, relu or tanh of its own, ONE output —
+evaluated once per trajectory on its final state, and `terminal_cost` is the tagged callable to hand to
+MPPI(..., terminal_cost=model.terminal_cost):
+    z1[j] = b1[j]; for i ascending: z1[j] = z1[j] + W1[j][i] * s[i];  h = act(z1)        (second hidden layer: the same over h)
+    V = b3; for j ascending: V = V + w3[j] * h[j]
+    terminal = quad_T + (weight * V)        or, with replace_terminal, weight * V alone (the callable then returns
+                                            weight * V - quad_T: the solver adds it behind the terminal call's quad_T)
+The value's input is the final state as the dynamics network produced it: the `angular` mask does NOT wrap it (a limit: a critic
+over an angle should be fitted on the unwrapped range the rollouts reach, or on a model whose dynamics keep the angle wrapped).
 """
 from __future__ import annotations
 
@@ -54,6 +65,19 @@ def _f32(a) -> np.ndarray:
 
 def _provider(owner):
     return owner.native_inputs()
+
+
+def _finite_weight(weight) -> float:
+    w = float(weight)
+    if not np.isfinite(w) or abs(w) > float(np.finfo(np.float32).max):
+        raise ValueError("the value's weight must be finite (in float32)")
+    return w
+
+
+def _copy_value(v):
+    if v is None:
+        return None
+    return dict(v, layers=tuple(a.copy() for a in v["layers"]), table=v["table"].copy())
 
 
 class MLPModel:
@@ -91,6 +115,8 @@ class MLPModel:
         self._ref_own_q = False     # its q half was given (False: it mirrors self.q)
         self._ref_mirrors = {}      # (device, dtype) -> the copy the callables read there, kept in step IN PLACE
         self.reference_version = 0
+        self._value = None          # the terminal value (set_value): a dict of its padded layers, table, flags and weight, or None
+        self.value_version = 0
 
     def set_angular(self, angular) -> None:
         """Which state components are angles: indices below the network's own state width, or None / () for none.  For the
@@ -175,6 +201,142 @@ class MLPModel:
         if q is not None and self._ref is not None and not self._ref_own_q:  # rows without weights of their own follow q
             self._ref[:, self.DS:self.DS + ds] = torch.as_tensor(np.array(self.q[:ds]), device=self._ref.device)
             self.reference_changed()
+
+    # ------------------------------------------------------------------ the learned terminal value
+    def set_value(self, weights, biases=None, activation: str = "tanh", weight: float = 1.0, replace_terminal: bool = False) -> None:
+        """A value network over the state: weights / biases per layer in torch.nn.Linear's layout — W1 [h1, ds], (W2 [h2, h1],)
+        W3 [1, h] with ds the network's own state width and h1, h2 <= 32; its activation and depth are its own.
+        terminal = quad_T + weight * V, or weight * V alone with replace_terminal.  set_value(None) switches it off.
+        ValueError for anything the device path does not take."""
+        if weights is None:
+            self._value = None
+            self.value_version += 1
+            return
+        if activation not in ("relu", "tanh"):
+            raise ValueError("activation must be 'relu' or 'tanh'")
+        w = _finite_weight(weight)
+        layers, hidden = self._value_layers(weights, biases)
+        self._value = {"layers": layers, "table": np.concatenate([a.reshape(-1) for a in layers]).astype(np.float32),
+                       "hidden_layers": hidden, "activation": activation, "weight": w, "replace_terminal": bool(replace_terminal)}
+        self._value_torch = {}
+        self.value_version += 1
+
+    def _value_layers(self, weights, biases):
+        Ws, bs = [_f32(a) for a in weights], [_f32(b).reshape(-1) for b in (biases or ())]
+        if len(Ws) != len(bs) or len(Ws) not in (2, 3):
+            raise ValueError("a value network with one or two hidden layers: 2 or 3 weight matrices and as many biases "
+                             f"(got {len(Ws)} and {len(bs)})")
+        if any(a.ndim != 2 for a in Ws) or any(a.shape[0] != b.shape[0] for a, b in zip(Ws, bs)):
+            raise ValueError("every weight is a matrix [out, in] with a bias [out]")
+        if any(a.shape[1] != p.shape[0] for p, a in zip(Ws[:-1], Ws[1:])):
+            raise ValueError("the layers do not chain: each weight's input width is the previous layer's output width")
+        ds, DS = self.dim_state_model, self.DS
+        if Ws[0].shape[1] != ds:
+            raise ValueError(f"the value network reads the state: input width {ds} (got {Ws[0].shape[1]})")
+        if Ws[-1].shape[0] != 1:
+            raise ValueError(f"the value network has ONE output (got {Ws[-1].shape[0]})")
+        if any(a.shape[0] > HIDDEN for a in Ws[:-1]):
+            raise ValueError(f"hidden layers of at most {HIDDEN} units run on the device")
+        if not all(np.all(np.isfinite(a)) for a in Ws + bs):
+            raise ValueError("weights and biases must be finite")
+        # the padded layers of the table: W1[32][DS], b1[32], W2[32][32], b2[32], w3[32], b3[1]
+        W1, b1 = np.zeros((HIDDEN, DS), np.float32), np.zeros(HIDDEN, np.float32)
+        W1[:Ws[0].shape[0], :ds] = Ws[0]
+        b1[:bs[0].shape[0]] = bs[0]
+        W2, b2 = np.zeros((HIDDEN, HIDDEN), np.float32), np.zeros(HIDDEN, np.float32)
+        if len(Ws) == 3:
+            W2[:Ws[1].shape[0], :Ws[1].shape[1]] = Ws[1]
+            b2[:bs[1].shape[0]] = bs[1]
+        w3, b3 = np.zeros(HIDDEN, np.float32), np.zeros(1, np.float32)
+        w3[:Ws[-1].shape[1]] = Ws[-1][0]
+        b3[:] = bs[-1]
+        return (W1, b1, W2, b2, w3, b3), len(Ws) - 1
+
+    def set_value_module(self, module: torch.nn.Module, **kw) -> None:
+        """set_value from nn.Sequential(Linear, act, [Linear, act,] Linear(., 1)) with act = nn.ReLU or nn.Tanh (one kind);
+        keywords: weight, replace_terminal."""
+        mods = list(module.children())
+        lin = [m for m in mods if isinstance(m, torch.nn.Linear)]
+        acts = [m for m in mods if not isinstance(m, torch.nn.Linear)]
+        kinds = {torch.nn.ReLU: "relu", torch.nn.Tanh: "tanh"}
+        shape_ok = (len(mods) == 2 * len(lin) - 1 and all(isinstance(m, torch.nn.Linear) for m in mods[0::2])
+                    and all(type(m) in kinds for m in acts))
+        if not shape_ok or len(lin) not in (2, 3) or len({type(m) for m in acts}) != 1 or any(m.bias is None for m in lin):
+            raise ValueError("set_value_module takes nn.Sequential(Linear, act, [Linear, act,] Linear(., 1)) with biases and "
+                             "act = nn.ReLU or nn.Tanh throughout")
+        self.set_value([m.weight for m in lin], [m.bias for m in lin], activation=kinds[type(acts[0])], **kw)
+
+    def update_value(self, weights, biases) -> None:
+        """New weights of the same depth for the value (a critic learned online); activation, weight and replace_terminal stay.
+        The solver uploads the table before its next solve, in stream order."""
+        if self._value is None:
+            raise ValueError("update_value: no value network is set (set_value)")
+        layers, hidden = self._value_layers(weights, biases)
+        if hidden != self._value["hidden_layers"]:
+            raise ValueError("update_value keeps the value network's number of layers")
+        self._value = dict(self._value, layers=layers, table=np.concatenate([a.reshape(-1) for a in layers]).astype(np.float32))
+        self._value_torch = {}
+        self.value_version += 1
+
+    def set_value_weight(self, weight: float) -> None:
+        """The weight of the value alone."""
+        if self._value is None:
+            raise ValueError("set_value_weight: no value network is set (set_value)")
+        w = _finite_weight(weight)
+        self._value = dict(self._value, weight=w)
+        self.value_version += 1
+
+    @property
+    def value(self):
+        """What set_value left: {"table", "hidden_layers", "activation", "weight", "replace_terminal", "layers"}, or None."""
+        return self._value
+
+    def _value_on(self, ref: torch.Tensor):
+        key = (ref.device, ref.dtype)
+        cache = self.__dict__.setdefault("_value_torch", {})
+        got = cache.get(key)
+        if got is None:
+            got = tuple(torch.tensor(np.array(a)).to(ref.device, ref.dtype) for a in self._value["layers"])
+            cache[key] = got
+        return got
+
+    def value_of(self, state: torch.Tensor) -> torch.Tensor:
+        """V(state) [N] in the device's operation order (plain torch; no weight)."""
+        if self._value is None:
+            raise ValueError("no value network is set (set_value)")
+        W1, b1, W2, b2, w3, b3 = self._value_on(state)
+        act = (torch.tanh if self._value["activation"] == "tanh" else (lambda z: torch.clamp_min(z, 0.0)))
+        n = state.shape[0]
+        z = b1.expand(n, HIDDEN)
+        for i in range(self.DS):
+            z = z + W1[:, i] * state[:, i:i + 1]
+        h = act(z)
+        if self._value["hidden_layers"] == 2:
+            z = b2.expand(n, HIDDEN)
+            for i in range(HIDDEN):
+                z = z + W2[:, i] * h[:, i:i + 1]
+            h = act(z)
+        v = b3.expand(n)
+        for j in range(HIDDEN):
+            v = v + w3[j] * h[:, j]
+        return v
+
+    @native_model(lambda owner: owner.model_name, "terminal", _provider)
+    def terminal_cost(self, state: torch.Tensor, info=None) -> torch.Tensor:
+        """What MPPI(..., terminal_cost=...) adds behind the terminal call of `cost`: weight * V(S_T) — with replace_terminal,
+        minus that call's quadratic, so that the sum is weight * V alone up to one rounding.  `info` (the solver's generic
+        path hands a tagged terminal callable the dict of its terminal call: t = T - 1) picks the row of a reference; without
+        it the table's last row."""
+        if self._value is None:
+            raise ValueError("terminal_cost: no value network is set (set_value)")
+        wv = self._value["weight"] * self.value_of(state)
+        if self._value["replace_terminal"]:
+            tab = self._ref_on(state)
+            if info is None and tab is not None:
+                info = {"t": tab.shape[0] - 1}
+            zero = torch.zeros(state.shape[0], self.dim_control, device=state.device, dtype=state.dtype)
+            return wv - self.cost(state, zero, info)
+        return wv
 
     # ------------------------------------------------------------------ weights
     def _set(self, weights, biases) -> None:
@@ -261,7 +423,8 @@ class MLPModel:
         return {"params": [float(v) for v in np.concatenate([self.goal, self.q, self.r])],
                 "mlp": {"table": self.table, "hidden_layers": self.hidden_layers, "activation": self.activation,
                         "residual": self.residual, "version": self.version, "angular": self.angular_mask,
-                        "reference": self._ref, "reference_version": self.reference_version}}
+                        "reference": self._ref, "reference_version": self.reference_version,
+                        "value": None if self._value is None else dict(self._value, version=self.value_version)}}
 
     # ------------------------------------------------------------------ the callables
     def _on(self, ref: torch.Tensor):
@@ -325,9 +488,9 @@ class MLPModel:
         new = object.__new__(type(self))
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            new.__dict__[k] = {} if k in ("_torch", "_ref_mirrors") else (tuple(a.copy() for a in v) if k == "layers" else
-                                                                          v.copy() if isinstance(v, np.ndarray) else
-                                                                          v.clone() if torch.is_tensor(v) else v)
+            new.__dict__[k] = {} if k in ("_torch", "_ref_mirrors", "_value_torch") else (
+                _copy_value(v) if k == "_value" else tuple(a.copy() for a in v) if k == "layers" else
+                v.copy() if isinstance(v, np.ndarray) else v.clone() if torch.is_tensor(v) else v)
         for a in (new.goal, new.q, new.r):
             a.flags.writeable = False
         return new
@@ -427,6 +590,28 @@ class MLPEnsemble:
             m._ref, m._ref_own_q, m._ref_mirrors = first._ref, first._ref_own_q, first._ref_mirrors
             m.reference_version = max(m.reference_version, first.reference_version) + 1
 
+    def set_value(self, weights, biases=None, **kw) -> None:
+        """MLPModel.set_value for every member: ONE value network per ensemble, shared by its members (checked on the first: a
+        refused network changes none).  A value per member is not built."""
+        self._members[0].set_value(weights, biases, **kw)
+        for m in self._members[1:]:
+            m.set_value(weights, biases, **kw)
+
+    def set_value_module(self, module, **kw) -> None:
+        self._members[0].set_value_module(module, **kw)
+        for m in self._members[1:]:
+            m.set_value_module(module, **kw)
+
+    def update_value(self, weights, biases) -> None:
+        self._members[0].update_value(weights, biases)
+        for m in self._members[1:]:
+            m.update_value(weights, biases)
+
+    def set_value_weight(self, weight: float) -> None:
+        self._members[0].set_value_weight(weight)
+        for m in self._members[1:]:
+            m.set_value_weight(weight)
+
     def set_angular(self, angular) -> None:
         """MLPModel.set_angular for every member (checked on the first: a refused mask changes none)."""
         self._members[0].set_angular(angular)
@@ -463,7 +648,8 @@ class MLPEnsemble:
 
     def __getattr__(self, name):  # (the architecture, as the members state it)
         if name in ("dim_state_model", "dim_control", "hidden_layers", "activation", "residual", "goal", "q", "r", "DS",
-                    "dim_state", "pad_state", "angular", "angular_mask", "reference", "reference_version"):
+                    "dim_state", "pad_state", "angular", "angular_mask", "reference", "reference_version",
+                    "value", "value_version", "value_of"):
             return getattr(self.__dict__["_members"][self.__dict__["_nominal"]], name)
         raise AttributeError(name)
 
@@ -481,6 +667,10 @@ class MLPEnsemble:
     @native_model(lambda owner: owner.model_name, "cost", _provider)
     def cost(self, state: torch.Tensor, action: torch.Tensor, info=None) -> torch.Tensor:
         return self._members[self._nominal].cost(state, action, info)
+
+    @native_model(lambda owner: owner.model_name, "terminal", _provider)
+    def terminal_cost(self, state: torch.Tensor, info=None) -> torch.Tensor:
+        return self._members[self._nominal].terminal_cost(state, info)
 
     def __deepcopy__(self, memo):
         import copy

@@ -109,7 +109,11 @@ class GenericPathMixin:
         info["prev_state"] = S[:, -2, :]
         zero_action = torch.zeros(N, self._dim_control, device=self._device, dtype=self._dtype)
         terminal = self._cost_func(S[:, -1, :], zero_action, info)
-        self._generic_costs_keep.copy_(torch.sum(costs, dim=1) + terminal)
+        total = torch.sum(costs, dim=1) + terminal
+        if self._terminal_cost is not None:  # the opt-in terminal-only term, behind the reference's own terminal call
+            extra = self._terminal_cost(S[:, -1, :], info) if self._terminal_takes_info else self._terminal_cost(S[:, -1, :])
+            total = total + extra.to(self._dtype).reshape(N)
+        self._generic_costs_keep.copy_(total)
 
     def _states_prediction_graphed(self) -> torch.Tensor:
         """Step 8 (the batch-1 rollout of the solution through the user's dynamics, T launch-bound calls) as a second

@@ -32,8 +32,9 @@ class ModuleProtocolMixin:
         memo[id(self)] = new
         dyn, cst = copy.deepcopy(self._dynamics, memo), copy.deepcopy(self._cost_func, memo)
         me, it = self.__dict__, new.__dict__
-        it["_dynamics"], it["_cost_func"] = dyn, cst
-        it["_ctor"] = dict(self._ctor, dynamics=dyn, cost_func=cst)  # (a copy of the copy starts from ITS callables, and the originals are not kept alive)
+        trm = copy.deepcopy(self._terminal_cost, memo)  # (the opt-in terminal term: a callable like the other two)
+        it["_dynamics"], it["_cost_func"], it["_terminal_cost"] = dyn, cst, trm
+        it["_ctor"] = dict(self._ctor, dynamics=dyn, cost_func=cst, terminal_cost=trm)  # (a copy of the copy starts from ITS callables, and the originals are not kept alive)
         if self._model is not None and self._recognized is None:
             d, c = resolve(dyn), resolve(cst)
             if d and c:

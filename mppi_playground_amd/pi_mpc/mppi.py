@@ -96,6 +96,7 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         noise_beta=0.0,
         risk: str = "mean",
         risk_alpha: float = 1.0,
+        terminal_cost: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
         _force_exchange: bool = False,
     ) -> None:
         """Arguments up to `seed` are the reference's (src/pi_mpc/mppi.py:24-47).
@@ -203,6 +204,16 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                 captured graph is replayed once per particle: it reads the start state from a static buffer) and one more
                 dynamics-only pass from the nominal state for `_state_seq_batch`.  ValueError for an unknown measure or
                 risk_alpha outside (0, 1].
+            terminal_cost: OPT-IN (default None: no code path, no launch, no result differs).  A callable
+                f(state[N, dim_state]) -> [N] evaluated on the FINAL state of every sample and added behind the reference's
+                own terminal call: cost_i = sum_t stage + cost_func(S_T, 0, info) + terminal_cost(S_T) — a term the
+                reference's plugin surface cannot express (its cost_func cannot tell the terminal call from a stage call).
+                Everything downstream (minimum, temperature rules, weights, get_top_samples, adapt_covariance, `_costs`,
+                every row of `particle_costs`) sees the sum.  It runs fused for ONE kind of callable: the learned value of
+                the model that owns dynamics and cost, MPPI(dynamics=m.dynamics, cost_func=m.cost,
+                terminal_cost=m.terminal_cost) with m an envs.MLPModel / MLPModel8 / MLPEnsemble (set_value).  Any other
+                callable — also next to a tagged native pair: the fused kernels do not export the final states — takes
+                the generic path (opaque callables; graph_callables captures it with the loops) and means the same thing.
             shard_samples: treat `num_samples` as the GLOBAL sample count and let this rank own the
                 contiguous block rank*N/W .. (rank+1)*N/W of it (torch.distributed must be
                 initialised); the 4+T*dc-float shard summaries are exchanged once per solve with one RCCL
@@ -226,7 +237,7 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
                           graph_callables=graph_callables, lazy_state_seq=lazy_state_seq, adapt_covariance=adapt_covariance,
                           cov_rate=cov_rate, cov_floor=cov_floor, sigma_min=sigma_min, sigma_max=sigma_max,
                           action_cost=action_cost, action_cost_weight=action_cost_weight, noise_beta=noise_beta,
-                          risk=risk, risk_alpha=risk_alpha, _force_exchange=_force_exchange)
+                          risk=risk, risk_alpha=risk_alpha, terminal_cost=terminal_cost, _force_exchange=_force_exchange)
         assert u_min.shape == (dim_control,)
         assert u_max.shape == (dim_control,)
         assert sigmas.shape == (dim_control,)
@@ -266,6 +277,9 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
         self._dim_control = dim_control
         self._dynamics = dynamics
         self._cost_func = cost_func
+        if terminal_cost is not None and not callable(terminal_cost):
+            raise ValueError("terminal_cost must be a callable f(state[N, dim_state]) -> [N], or None")
+        self._terminal_cost = terminal_cost
         self._u_min = u_min.clone().detach().to(self._device, self._dtype)
         self._u_max = u_max.clone().detach().to(self._device, self._dtype)
         self._sigmas = sigmas.clone().detach().to(self._device, self._dtype)
@@ -329,6 +343,20 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             # a model whose dynamics are its owner's DATA (envs.MLPModel: the weights): the device would take table and
             # parameters from the cost callable's owner only — two different owners are two different models
             dyn = cst = None
+        # A terminal-only term (terminal_cost): the fused kernels carry ONE kind — the learned value of the model that owns
+        # dynamics and cost (envs.MLPModel.terminal_cost: all three from one owner).  Any other callable needs the final states,
+        # which the fused kernels do not export: the triple takes the generic path and means the same thing.
+        self._terminal_fused = False
+        self._terminal_takes_info = False  # a tagged terminal callable is handed the dict of the terminal call (t = T - 1)
+        if terminal_cost is not None:
+            trm = resolve(terminal_cost)
+            self._terminal_takes_info = bool(trm and trm[0].role == "terminal")
+            if (dyn and cst and trm and trm[0].role == "terminal" and trm[0].model == cst[0].model == dyn[0].model
+                    and getattr(trm[0], "per_owner", False) and trm[1] is cst[1] and trm[1] is dyn[1]):
+                self._terminal_fused = True
+            else:
+                dyn = cst = None
+                self._recognized = None
         if (dyn and cst and dyn[0].model == cst[0].model and dyn[0].role == "dynamics"
                 and cst[0].role == "cost"):
             self._model = dyn[0].model  # fused on the device
@@ -622,6 +650,17 @@ class MPPI(ModuleProtocolMixin, ExchangeMixin, GenericPathMixin, QueriesMixin, n
             if getattr(self._h, "mlp_reference_key", None) != key:  # (kept on the handle: a new one starts without a reference)
                 self._put_mlp_reference(table)
                 self._h.mlp_reference_key = key
+            # the learned terminal value: only a solver that was given the model's terminal_cost carries it
+            value = mlp.get("value") if self._terminal_fused else None
+            if self._terminal_fused and value is None:
+                raise ValueError("terminal_cost: the model has no value network (set_value)")
+            key = None if value is None else (id(self._cost_owner), value["version"])
+            if getattr(self._h, "mlp_value_key", None) != key:  # (kept on the handle: a new one starts without a value)
+                tab = np.ascontiguousarray(value["table"], dtype=np.float32)
+                self._h.call("mppi_set_mlp_value", tab.ctypes.data_as(C.c_void_p), int(tab.size), int(value["hidden_layers"]),
+                             _capi.MLP_ACTIVATIONS[value["activation"]], float(value["weight"]), int(bool(value["replace_terminal"])),
+                             self._stream())
+                self._h.mlp_value_key = key
         discs = spec.get("discs")
         if discs is not None:  # moving discs: the predicted table travels again whenever its owner bumped the version
             key = (id(self._cost_owner), discs["version"])

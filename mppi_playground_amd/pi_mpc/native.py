@@ -9,7 +9,10 @@ call site `MPPI(..., dynamics=env.dynamics, cost_func=ctrl.cost_function)` stays
 
 where `provider(owner)` returns the model's current inputs as plain host data:
     {"params": [floats], "maps": [GridSpec, ...], "ref_path": ndarray[rows,4] | None,
-     "mlp": {"table": float32[n], "hidden_layers": 1 | 2, "activation": "relu" | "tanh", "residual": bool, "version": int},
+     "mlp": {"table": float32[n], "hidden_layers": 1 | 2, "activation": "relu" | "tanh", "residual": bool, "version": int,
+             "value": None | {"table": float32[32 * DS + 1121], "hidden_layers": 1 | 2, "activation": ..., "weight": float,
+                              "replace_terminal": bool, "version": int}   (the learned terminal value: uploaded by version, and
+                              only by a solver that was given the model's callable of role "terminal" as `terminal_cost`)},
      "discs": {"table": float32 [rows, n, 4] = {cx, cy, r2, w} per horizon step (a torch tensor on the solver's device, or
                an ndarray), "version": int,
                "soft": {"reach": float > 1, "skirt": float in [0, 1]}  (the soft disc models only)}}
@@ -36,7 +39,7 @@ import numpy as np
 class NativeTag:
     model: object                 # a key of _capi.MODEL_IDS ("pendulum", "racing", ...), or model(owner) -> such a key
                                   # (resolve() calls it: envs/mlp_model.py picks "mlp41" / "mlp42" / "mlp81" / ... by its widths)
-    role: str                     # "dynamics" | "cost"
+    role: str                     # "dynamics" | "cost" | "terminal" (MPPI(terminal_cost=): envs.MLPModel.terminal_cost)
     provider: Optional[Callable]  # provider(owner) -> dict
     per_owner: bool = False       # the model name came from the owner (below): dynamics and cost must share ONE owner
 
