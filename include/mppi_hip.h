@@ -816,6 +816,14 @@ int mppi_p2p_error(mppi_handle_t h);
  * (statistics pass + select step; round 1 always is: it returns at once when round 0 finished the search) — same
  * temperature to the bit, measured no faster (default 0); "timing" (see mppi_get_timing). */
 int mppi_set_option(mppi_handle_t h, const char* key, int64_t value);
+/* The math level the NEXT rollout of this handle dispatches, into *level_out: 0 = library math and bounds-tested map lookups,
+ * 1 = the range-checked fast paths (nav2d / racing: the padded-grid lookup), 2 = 1 + hardware sin/cos of the wrapped headings.
+ * It is option "math" (clamped to 0..2) unless a launch-uniform precondition of the model's fast kernels does not hold — solver
+ * bounds beyond the model's own action clamp, heading increments of pi or more, racing steering beyond 0.25 or a wheel base
+ * whose reciprocal is unusable, a cell size with an all-ones significand, position limits that reach beyond one cell past the
+ * map, racing maps of different geometry, a map or the parameters not set yet — then it is 0 whatever the option says.
+ * Read-only: no setter, no device work, no change of behaviour. */
+int mppi_get_math_level(mppi_handle_t h, int* level_out);
 /* Device time per stage from HIP event pairs since the last drain (no host synchronisation while recording).  The
  * events ride on the stage's own dispatches: a stage time runs from the begin of its first kernel to the end of its
  * last, without the wait between a stream marker and the dispatch (a captured stream, and a stage that ends in a

@@ -57,6 +57,7 @@ SYMBOLS = [
     "mppi_essps_get_state", "mppi_essps_set_state",
     "mppi_set_mlp_reference", "mppi_get_mlp_reference", "mppi_set_mlp_angular", "mppi_get_mlp_angular",
     "mppi_set_mlp_value", "mppi_get_mlp_value",
+    "mppi_get_math_level",
 ]
 
 
@@ -202,7 +203,8 @@ def load(allow_missing=()):
     for name, types in (("mppi_set_mlp_reference", [vp, vp, i32, i32, vp]), ("mppi_get_mlp_reference", [vp, vp, vp, i32, vp]),
                         ("mppi_set_mlp_angular", [vp, u32]), ("mppi_get_mlp_angular", [vp, vp]),
                         ("mppi_set_mlp_value", [vp, vp, i32, i32, i32, f32, i32, vp]),
-                        ("mppi_get_mlp_value", [vp, vp, vp, vp, vp, vp, vp, vp])):
+                        ("mppi_get_mlp_value", [vp, vp, vp, vp, vp, vp, vp, vp]),
+                        ("mppi_get_math_level", [vp, vp])):
         if not (name in allow_missing and not hasattr(lib, name)):
             getattr(lib, name).argtypes = types
     for name in SYMBOLS:

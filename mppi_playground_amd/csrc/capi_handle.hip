@@ -457,6 +457,12 @@ int mppi_set_option(mppi_handle_t h, const char* key, int64_t value) {
     return fail(h, MPPI_E_INVALID, "unknown option " + k);
 }
 
+int mppi_get_math_level(mppi_handle_t h, int* level_out) {
+    if (!h || !level_out) return fail(h, MPPI_E_INVALID, "null");
+    *level_out = math_level(h);
+    return MPPI_OK;
+}
+
 // mean device time [ms] and launch count of the stand-alone state-sequence kernel (mppi_join_state_seq; the rollouts that
 // rode in a rollout launch are not separate kernels) since the last call (option "timing" = 1)
 int mppi_get_state_seq_timing(mppi_handle_t h, float* out2) {

@@ -15,7 +15,9 @@ def lib():
     if _lib is None:
         src = os.path.join(_HERE, "emul.cpp")
         hdr = os.path.join(_HERE, "..", "..", "mppi_playground_amd", "csrc", "mppi_models.hpp")
-        if (not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(src), os.path.getmtime(hdr))):
+        inc = os.path.join(os.path.dirname(hdr), "mppi_models.inc")  # (the functors' bodies: included by the header)
+        if (not os.path.exists(_SO)
+                or os.path.getmtime(_SO) < max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(inc))):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma",
                                    "-o", _SO, src])
         _lib = C.CDLL(_SO)
@@ -47,6 +49,24 @@ def rollout_cost(model_id, fast, x0, mean, eps, u_min, u_max, threshold, params=
                                  0 if r is None else r.shape[0], _p(costs), _p(bad), _p(S))
     assert rc == 0
     return costs, bad, S
+
+
+def map_lookup(grids, cell, origin, x_lim, y_lim, pts):
+    """The header's map lookups on one geometry (emul_map_lookup): grids = (obstacle,) or (obstacle, lane) [nx][ny] uint8.
+    -> dict(plan, usable, koff, pad, fast, lib); pad / fast hold -1 where the kernels would not take that lookup."""
+    f32 = np.float32
+    g0 = np.ascontiguousarray(grids[0], np.uint8)
+    g1 = np.ascontiguousarray(grids[1], np.uint8) if len(grids) > 1 else None
+    pts = np.ascontiguousarray(pts, f32).reshape(-1, 2)
+    lim = np.array([x_lim[0], x_lim[1], y_lim[0], y_lim[1]], f32)
+    koff = C.c_uint32(0)
+    pad, fast, ref = (np.empty(len(pts), f32) for _ in range(3))
+    fn = lib().emul_map_lookup
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                   C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = fn(_p(g0), _p(g1), g0.shape[0], g0.shape[1], float(cell), float(origin[0]), float(origin[1]), _p(lim), _p(pts),
+            len(pts), C.byref(koff), _p(pad), _p(fast), _p(ref))
+    return dict(plan=bool(rc & 1), usable=bool(rc & 2), koff=int(koff.value), pad=pad, fast=fast, lib=ref)
 
 
 _SEARCH_SO = os.path.join(_HERE, "libsearch.so")

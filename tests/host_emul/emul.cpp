@@ -133,6 +133,60 @@ int emul_rollout_cost(int model, int fast, int N, int T, int threshold, const fl
     return 0;
 }
 
+// The map lookups of the nav2d / racing cost kernels on one geometry (tests/lookup_cases.py), each as the header defines it:
+// the plan of the padded grid for the position limits lim = {xlo, xhi, ylo, yhi} (pad_map_plan: verdict and koff), the padded
+// lookup on a grid built the way pad_map_kernel builds it (map1: racing's lane grid, summed in; ring = 1 or 2) and addressed
+// through a base pointer koff below it as refresh_pad leaves it, and the bounds-tested lookup with Markstein's and with the
+// IEEE quotient.  inv_cell is prepare_map's (0 for a cell size whose significand is all ones: no fast lookups then).
+// Returns bit 0: the plan is accepted, bit 1: inv_cell is usable.  pad_out is written (else -1) for the points inside the
+// limits when both hold — the only ones the kernels hand to occ_lookup_pad — and fast_out (else -1) when bit 1 holds.
+int emul_map_lookup(const uint8_t* map0, const uint8_t* map1, int nx, int ny, float cell, float ox, float oy, const float* lim,
+                    const float* pts, int64_t n, uint32_t* koff_out, float* pad_out, float* fast_out, float* lib_out) {
+    ModelCtx ctx;
+    std::memset(&ctx, 0, sizeof(ctx));
+    const uint8_t* mp[2] = {map0, map1};
+    uint32_t bits; std::memcpy(&bits, &cell, 4);
+    const bool all_ones = (bits & 0x7fffffu) == 0x7fffffu;
+    for (int sidx = 0; sidx < 2; ++sidx) {
+        MapView& m = ctx.maps[sidx];
+        m.cells = mp[sidx]; m.nx = nx; m.ny = ny; m.cell = cell; m.ox = ox; m.oy = oy;
+        m.inv_cell = all_ones ? 0.0f : 1.0f / cell;
+    }
+    uint32_t koff = 0;
+    const bool plan = pad_map_plan(ctx.maps[0], lim[0], lim[1], lim[2], lim[3], koff);
+    if (koff_out) *koff_out = koff;
+    std::vector<uint8_t> pad;
+    const bool padded = plan && !all_ones;
+    if (padded) {
+        pad.resize((size_t)(nx + 1) * (ny + 1));
+        for (int ix = 0; ix <= nx; ++ix)
+            for (int iy = 0; iy <= ny; ++iy) {  // one thread of pad_map_kernel
+                uint8_t v = map1 ? 2 : 1;
+                if (ix < nx && iy < ny) {
+                    v = map0[(size_t)ix * ny + iy];
+                    if (map1) v = (uint8_t)(v + map1[(size_t)ix * ny + iy]);
+                }
+                pad[(size_t)ix * (ny + 1) + iy] = v;
+            }
+        ctx.pad = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(pad.data()) - (uintptr_t)koff);
+        ctx.pad_stride = ny + 1;
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        const float px = pts[2 * i], py = pts[2 * i + 1];
+        const bool inside = px >= lim[0] && px <= lim[1] && py >= lim[2] && py <= lim[3];
+        pad_out[i] = padded && inside ? mppi::strict::occ_lookup_pad(ctx, ctx.maps[0], px, py) : -1.0f;
+        float f = -1.0f, l = 0.0f;
+        for (int sidx = 0; sidx < (map1 ? 2 : 1); ++sidx) {
+            const MapView& m = ctx.maps[sidx];
+            if (!all_ones) f = (sidx ? f : 0.0f) + mppi::strict::occ_lookup<true>(m, m.cells, px, py, 1.0f);
+            l += mppi::strict::occ_lookup<false>(m, m.cells, px, py, 1.0f);
+        }
+        fast_out[i] = f;
+        lib_out[i] = l;
+    }
+    return (plan ? 1 : 0) | (all_ones ? 0 : 2);
+}
+
 // element-wise pins of the fast math against the library math
 using namespace mppi::strict;  // element-wise pins: same functions in both contraction variants
 void emul_sincos(const float* x, float* s, float* c, int n, int fast) {
